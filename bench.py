@@ -11,8 +11,13 @@ Default workload at N>1: BASELINE.json configs[4] -- the NiceInstrument swarm (O
 fused, voice mixdown in the same kernel), 131,072 voices per GPU (1,048,576 at N=8), two output
 channels, with the one exchange step of the multi-GPU path in the timed region: the GPUs'
 partial mixes are summed by an RCCL all-reduce over xGMI, one collective per 48-buffer batch.
-The N=1 line carries the same 131,072-voice shard without the collective in `config5_shard`,
-and the N>1 line times it again on every rank (`single_gpu_shard`) for the scaling factor.
+
+A plain run sets up, warms up, times exactly --steps steps (whole 48-buffer patterns for the
+note-pattern workloads) and prints the line; `--dump-outputs DIR` also writes what the last
+timed step painted.  Everything else is `--full`: further timed regions, the oracle parity
+checks, the CPU baseline, and at N=1 config 4, the one-launch-per-step form and the same
+131,072-voice shard without the collective (`config5_shard`); at N>1 the exchange timings and
+the shard timed again on every rank (`single_gpu_shard`) for the scaling factor.
 
 Launching: `python bench.py --gpus N` starts N ranks itself (fresh child processes, started
 before anything touches a GPU; rank 0's line is relayed); under `torch.distributed.run`
@@ -93,7 +98,20 @@ def parse(argv=None):
                          "signal's peak instead of bits; csrc/filter_tp.hip.h); script: the module's sines that may be f32; the line says so in config.tolerant")
     ap.add_argument("--eager", action="store_true", help="one host launch per step instead of hipGraph replay")
     ap.add_argument("--pad-voices", type=int, default=None, help="row padding of the output images in voices (default: the library's choice, Context.image)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: further timed regions (--repeats), the oracle parity checks, the CPU baseline, "
+                         "config 4 / config 5 and the one-launch-per-step form at N=1, the exchange timings and the scaling factor at N>1. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step painted (rank 0) as DIR/<name>.npy, float32: `output` = "
+                         "the [frames][voices] image (a fixed, seeded sample of the voices above 60 MiB, their indices in `output_voices`), "
+                         "or for nice_mix the [channels][frames] mix")
+    args = ap.parse_args(argv)
+    if args.repeats and not args.full:
+        ap.error("--repeats times further regions: it needs --full")
+    if args.p2p_compare and not args.full:
+        ap.error("--p2p-compare is a comparison beside the line: it needs --full")
+    return args
 
 
 def spawn_ranks(n, argv):
@@ -354,6 +372,19 @@ class Workload:
             if steps and steps % cand == 0:
                 return cand
         return g
+
+    def snapshot(self):
+        """What one step carries to the next (module state, ring and note-pattern positions).  main() puts it back before the
+        timed region, so that what the region paints does not depend on how many untimed regions ran before it."""
+        mods = [self.noise, self.flt] if self.name == "noise_filter" else [self.m]
+        return mods, [m.get_state() if hasattr(m, "get_state") else m.state() for m in mods], self.i, getattr(self, "nsteps", None)
+
+    def restore(self, snap):
+        mods, states, self.i, nsteps = snap
+        for m, st in zip(mods, states):
+            m.set_state(st)
+        if nsteps is not None:
+            self.nsteps = nsteps
 
     def _next(self):
         o = self.ring[self.i]
@@ -889,6 +920,24 @@ def build_record(lib):
     return rec
 
 
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: at most this much of an image; above it a fixed sample of its voices
+
+
+def dump_outputs(d, wl, out):
+    """--dump-outputs DIR: `out` (the last timed step's image or mix, on the device) as DIR/output.npy, float32.  An image larger than
+    DUMP_MAX_BYTES is cut to a sample of its voices drawn with a fixed seed (the same voices in every run of the same arguments),
+    their indices in DIR/output_voices.npy (float64, exact)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    if wl.name != "nice_mix" and out.numel() * 4 > DUMP_MAX_BYTES:
+        n = max(1, DUMP_MAX_BYTES // (out.shape[0] * 4))
+        voices = np.sort(np.random.default_rng(20240915).choice(out.shape[1], size=n, replace=False))
+        out = out[:, torch.from_numpy(voices).to(out.device)]
+        np.save(os.path.join(d, "output_voices.npy"), voices.astype(np.float64))
+    np.save(os.path.join(d, "output.npy"), np.ascontiguousarray(out.cpu().numpy(), dtype=np.float32))
+
+
 def dry_run(args, world, rank):
     """ZH_BENCH_EMULATE=1 on a box WITHOUT a GPU: the launcher, the rendezvous and the exchange step with host tensors
     (gloo).  Nothing is painted and nothing is measured: `value` is 0 and the line says so.  Used by the CPU tests."""
@@ -1078,6 +1127,7 @@ def main():
             # (event records captured INTO the graph would take two host calls off the timed path, but hipEventElapsedTime
             # refuses events recorded by graph nodes on this ROCm: "invalid resource handle", profiles/r04/probe_region.txt)
             self.ev0, self.ev1 = make_event(), make_event()
+            self.last_eager = True                   # the last step painted was an eager one (else the last buffer of a replay)
 
         def run_steps(self, n):
             wl, G, done = self.wl, self.G, 0
@@ -1091,11 +1141,22 @@ def main():
                 wl.step()
             if n - done and self.with_exchange:
                 wl.exchange()
+            if n:
+                self.last_eager = n > done
+
+        def last_output(self):
+            """The device array the last step of the last run_steps() painted: its [frames][voices] image, or for the mixdown
+            workload its [channels][frames] mix (after the exchange).  A replay's buffer j lands in ring[(first + j) % nring]."""
+            wl = self.wl
+            if wl.name == "nice_mix":
+                return wl.mixes[(wl.nsteps - 1) % 48 if self.last_eager else (self.G - 1) % 48]
+            return wl.ring[(wl.i - 1) % wl.nring if self.last_eager else (wl.graph_first_image + self.G - 1) % wl.nring]
 
         def warm(self, n):
             self.run_steps(n)
             if self.graph is not None and n < self.G:
                 self.graph.launch()                      # untimed: the first replay of a graph uploads it
+                self.last_eager = False
                 if self.with_exchange:
                     self.wl.exchange()
             torch.cuda.synchronize()
@@ -1123,6 +1184,7 @@ def main():
                 r2 = rec(h, e1)
                 sync()
                 elapsed = time.perf_counter() - t0
+                self.last_eager = False
                 for r, what in ((r0, "zh_event_record"), (r1, "zh_graph_launch"), (r2, "zh_event_record")):
                     abi.check(r, what)
             else:
@@ -1183,30 +1245,44 @@ def main():
     mixdown = args.workload == "nice_mix"
     main_run = Runner(args.workload, V, K, exchange=args.exchange, slots=(args.exchange == "p2p" and dist_on and mixdown))
     wl, G, graph = main_run.wl, main_run.G, main_run.graph
+    t_warm = time.perf_counter()
     main_run.warm(args.warmup)
+    warm_steps = args.warmup + (G if G and args.warmup < G else 0)
+    est_step = max_over_ranks(time.perf_counter() - t_warm) / warm_steps if warm_steps else None
     # Untimed rehearsals of the timed region, same code path: the W warm-up steps of a 4 us kernel are 20 us of
     # device work after seconds of set-up, and the first region then ran on a GPU and a host path still coming out of idle -- 7 %
     # slower than the median of the repeats, 111 against 98 us after 200 ms of idle in tools/probe_region.py.  At least 3 regions
-    # and 25 ms; nothing from them enters the line except their count.
-    def rehearse(run, k):
-        if args.no_rehearsal:
+    # and 25 ms; nothing from them enters the line except their count.  A region of a second or more (by the warm-up's time per
+    # step, or once one has run) is not rehearsed further: it is past the ramp on its own, and a rehearsal would cost 3 x --steps.
+    def rehearse(run, k, est=None):
+        if args.no_rehearsal or (est is not None and est * k >= 1.0):
             return 0
-        e3 = sum(run.region(k)[0] for _ in range(3))               # max over ranks: the same number on every rank,
-        n = 3 + min(997, max(0, int((0.025 - e3) / (e3 / 3))))      # so every rank runs the same count of regions
+        es = [run.region(k)[0]]                                     # max over ranks: the same number on every rank,
+        while len(es) < 3 and sum(es) < 1.0:                        # so every rank runs the same count of regions
+            es.append(run.region(k)[0])
+        if len(es) < 3:
+            return len(es)
+        e3 = sum(es)
+        n = 3 + min(997, max(0, int((0.025 - e3) / (e3 / 3))))
         for _ in range(n - 3):
             run.region(k)
         return n
-    rehearsals = rehearse(main_run, K)
+    start = main_run.wl.snapshot()
+    rehearsals = rehearse(main_run, K, est_step)
+    main_run.wl.restore(start)                       # the timed region starts from the same state whatever the rehearsals did
     elapsed, ev_ms = main_run.region(K)              # THE timed region of the contract: exactly K steps
     step_ms_events = ev_ms / K
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, main_run.last_output())
 
     # Further regions of exactly K steps, each bracketed the same way: a short region (the driver's 20 steps of a
     # 4 us kernel = 0.1 ms) is dominated by the launch ramp and the synchronize, and one sample of it is noisy.
     # With several GPUs every repeat is a PAIR -- the region with the exchange, then the same K steps without it -- so that
     # `single_gpu_shard` and `scaling_factor` are medians of interleaved regions, never one sample each.
+    # All of them --full only.
     import statistics
-    paired = dist_on and mixdown
-    R = args.repeats if args.repeats is not None else (min(30, max(0, int(0.5 / max(elapsed, 1e-4)))) if elapsed < 0.1 else 0)
+    paired = dist_on and mixdown and args.full
+    R = 0 if not args.full else args.repeats if args.repeats is not None else (min(30, max(0, int(0.5 / max(elapsed, 1e-4)))) if elapsed < 0.1 else 0)
     if paired:
         R = max(R, 5)
     reps = None
@@ -1296,7 +1372,7 @@ def main():
         out["repeats"] = reps
 
     if dist_on and mixdown:
-        # ---- the exchange step on its own, and the same shard without it (scaling factor) ----
+        # ---- the exchange step on its own, and the same shard without it (scaling factor); a plain run only names it ----
         rows = wl.batch_rows
         nbytes = wl.mixes[:rows].numel() * 4
         n_ex = 24
@@ -1318,9 +1394,6 @@ def main():
                 per = t.tolist()
             per = [x * 1e6 for x in per]
             return {"median": statistics.median(per), "min": min(per), "max": max(per), "samples": n_ex}
-        reduce_stat = time_exchange(wl.exchange)
-        reduce_us = reduce_stat["median"]
-        seen = torch.ones(1, device="cpu" if emulate else "cuda"); dist.all_reduce(seen)
         if wl.slots is not None:
             backend, kind = "host barriers + HIP IPC", "direct stores into the root's slots + rank-ordered sum (zh_sum_slots), host barriers"
         elif wl.comm is not None:
@@ -1328,11 +1401,15 @@ def main():
             kind = "all_reduce(sum) on the launch stream (C ABI zh_comm_*; torch.distributed carried the 128-byte id only)"
         else:
             backend, kind = "torch.distributed " + dist.get_backend(), "all_reduce(sum)"
-        out["collective"] = {"backend": backend, "kind": kind, "world_size_seen": int(seen.item()),
-                             "bytes": nbytes, "per": f"{rows}-buffer batch", "reduce_us": reduce_us, "reduce_us_spread": reduce_stat,
-                             "in_timed_region": True, "reduce_us_per_buffer": reduce_us / rows}
+        out["collective"] = {"backend": backend, "kind": kind, "bytes": nbytes, "per": f"{rows}-buffer batch", "in_timed_region": True}
         if comm_note:
             out["collective"]["note"] = comm_note
+    if dist_on and mixdown and args.full:
+        reduce_stat = time_exchange(wl.exchange)
+        reduce_us = reduce_stat["median"]
+        seen = torch.ones(1, device="cpu" if emulate else "cuda"); dist.all_reduce(seen)
+        out["collective"].update({"world_size_seen": int(seen.item()), "reduce_us": reduce_us, "reduce_us_spread": reduce_stat,
+                                  "reduce_us_per_buffer": reduce_us / rows})
         if wl.slots is None:
             # the same sum as ONE COLLECTIVE PER BUFFER (4-8 KiB each, the reference's per-buffer mix) -- which
             # granularity is latency-bound: `rows` small collectives against one of rows x the bytes
@@ -1393,12 +1470,12 @@ def main():
                 out["p2p_direct"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             dog.cancel()
 
-    if mixdown:
+    if mixdown and args.full:
         bt = time_batched(main_run, G if G else 48)
         if bt:
             out["batched_launches"] = bt
 
-    if world == 1 and args.workload == "pulseosc" and not args.eager and main_run.graph_held:
+    if args.full and world == 1 and args.workload == "pulseosc" and not args.eager and main_run.graph_held:
         # The same K steps recorded WITHOUT ZH_CAPTURE_COALESCE: one kernel node per step, each a launch of one 16 MiB buffer that
         # hands its phase counters to the next (the round-4 headline form).  Extra key, measured the same way as `value`.
         io = Runner("pulseosc", V, K, coalesce=False)
@@ -1413,7 +1490,7 @@ def main():
                                       "what": "the same steps recorded without ZH_CAPTURE_COALESCE (`value` of rounds 1-4 was this form)"}
         io.close()
 
-    if world == 1 and not args.no_config5 and args.workload == "pulseosc" and V == 4096:
+    if args.full and world == 1 and not args.no_config5 and args.workload == "pulseosc" and V == 4096:
         # the 1-GPU shard of config 5 (what every rank of the N>1 run renders), for the scaling ratio
         c5 = Runner("nice_mix", 131072, 96)
         c5.warm(48)
@@ -1445,13 +1522,13 @@ def main():
                 out["config5_shard"]["tolerant_form"]["parity"] = parity_check_mix(c5t.wl, ctx)
             c5t.close()
 
-    if world == 1 and not args.no_config4 and not args.no_config5 and args.workload == "pulseosc" and V == 4096:
+    if args.full and world == 1 and not args.no_config4 and not args.no_config5 and args.workload == "pulseosc" and V == 4096:
         try:
             out["config4"] = config4_record(ctx, with_oracle=not args.no_cpu)
         except Exception as e:          # noqa: BLE001  (an extra key: reported, never fatal)
             out["config4"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    if rank == 0 and not args.no_parity and (world == 1 or mixdown):
+    if args.full and rank == 0 and not args.no_parity and (world == 1 or mixdown):
         # (N > 1: rank 0's shard of the mixdown workload; local launches only, the other ranks wait at the last barrier)
         out["parity"] = parity_check_mix(wl, ctx) if mixdown else parity_check(wl, ctx)
         if world == 1 and graph is not None and not mixdown:
@@ -1459,7 +1536,7 @@ def main():
             pg = parity_check_graph(main_run, ctx)
             if pg:
                 out["parity_of_a_graph_replay"] = pg
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cb = cpu_baseline(args, wl)
         if cb:
             out["cpu_baseline"] = cb
@@ -1467,7 +1544,7 @@ def main():
     if world == 1 and "config5_shard" in out:
         out["scaling_anchor"] = ("config5_shard.value of THIS line (one GPU's shard of config 5, no exchange) is what the N > 1 lines' `value` / N compares with; "
                                  "`value` here is config 2 (4,096 PulseOsc voices), a different workload: value(N) / value(1) is meaningless")
-    elif dist_on and mixdown:
+    elif dist_on and mixdown and args.full:
         out["scaling_anchor"] = ("this line's own `scaling_factor` (world x time without the exchange / time with it) and `single_gpu_shard`, or the N = 1 line's "
                                  "`config5_shard.value`; the N = 1 line's `value` is config 2, a different workload")
     main_run.close()

@@ -98,7 +98,7 @@ def test_two_emulated_ranks_on_one_gpu_run_the_whole_multi_gpu_path(exchange):
     standing in for RCCL (two ranks on one device cannot form an RCCL communicator: tests/test_cpp_host.py) and, for
     `--exchange p2p`, the HIP-IPC slot exchange between the two processes."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--voices", "8192", "--exchange", exchange,
-                        "--repeats", "2"], capture_output=True, text=True, timeout=540, env=_env(ZH_BENCH_EMULATE="1"))
+                        "--repeats", "2", "--full"], capture_output=True, text=True, timeout=540, env=_env(ZH_BENCH_EMULATE="1"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _last_json(r.stdout)
     # `--steps 20` on the note-pattern workload = one whole 48-buffer pattern (the release stage is inside the timed region)
@@ -161,7 +161,7 @@ def test_the_drivers_own_command_line_for_n_ranks_on_a_gpu_box():
     prints exactly one JSON line with the whole N > 1 structure, the other rank prints nothing on stdout, exit code 0."""
     port = _free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--voices", "8192"],
+                        "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--voices", "8192", "--full"],
                        env=_env(ZH_BENCH_EMULATE="1"), capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -183,7 +183,7 @@ def test_one_rank_takes_the_real_rccl_path_of_the_n_rank_line():
     RCCL communicator: that half runs over gloo in the tests above.)"""
     port = _free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), BENCH, "--gpus", "1", "--steps", "20", "--warmup", "5", "--voices", "8192", "--no-cpu"],
+                        "--master-port", str(port), BENCH, "--gpus", "1", "--steps", "20", "--warmup", "5", "--voices", "8192", "--no-cpu", "--full"],
                        env=_env(ZH_BENCH_ONE_RANK_DIST="1"), capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -192,3 +192,85 @@ def test_one_rank_takes_the_real_rccl_path_of_the_n_rank_line():
     assert c["world_size_seen"] == 1 and c["reduce_us"] > 0 and "rccl" in (c["backend"] + c.get("kind", "")).lower(), c
     assert "zh_comm" in json.dumps(c) or "library" in json.dumps(c), c          # the library's communicator, not the torch fallback
     assert d["scaling_factor"] > 0 and d["parity"]["bitexact"] is True
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_tests", BENCH)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_extra_measurements_need_full():
+    """--repeats N and --p2p-compare are measurements beside the line: a plain run refuses them instead of ignoring them."""
+    b = _bench_module()
+    for argv in (["--repeats", "3"], ["--p2p-compare"]):
+        with pytest.raises(SystemExit):
+            b.parse(argv)
+        assert b.parse(argv + ["--full"]).full
+    assert not b.parse(["--steps", "20", "--warmup", "5"]).full
+    assert b.parse(["--repeats", "0"]).repeats == 0
+
+
+def test_dump_outputs_writes_f32_within_the_size_cap(tmp_path):
+    """--dump-outputs: a mix as it is; an image over the cap as a seeded sample of its voices, the same one every time."""
+    import types
+    import numpy as np
+    import torch
+    b = _bench_module()
+    mix = torch.arange(2 * 1024, dtype=torch.float32).reshape(2, 1024)
+    b.dump_outputs(str(tmp_path / "mix"), types.SimpleNamespace(name="nice_mix"), mix)
+    got = np.load(tmp_path / "mix" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, mix.numpy()) and not (tmp_path / "mix" / "output_voices.npy").exists()
+    F, V = 1024, 16384 + 1000
+    img = torch.arange(F * V, dtype=torch.float32).reshape(F, V)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), types.SimpleNamespace(name="pulseosc"), img)
+    out, voices = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "a" / "output_voices.npy")
+    assert out.dtype == np.float32 and voices.dtype == np.float64
+    assert out.nbytes + voices.nbytes <= 64 << 20 and out.shape == (F, len(voices)) and np.all(np.diff(voices) > 0)
+    assert np.array_equal(out, img.numpy()[:, voices.astype(np.int64)])
+    assert np.array_equal(voices, np.load(tmp_path / "b" / "output_voices.npy")) and np.array_equal(out, np.load(tmp_path / "b" / "output.npy"))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("workload", ["pulseosc", "nice_mix"])
+def test_plain_run_is_lean_and_its_dumped_outputs_repeat(workload, tmp_path):
+    """A plain run prints the headline and nothing measured beside it; `--dump-outputs` gives the same arrays in two runs of the
+    same arguments (the timed region starts from the same state however many rehearsal regions ran).  PulseOsc: the dump is the
+    65th buffer painted from the initial state (20 eager steps before the graph is captured, 5 warm-up steps and the graph's
+    first replay, 20 timed steps), checked against the oracle on a few voices."""
+    import numpy as np
+    extra = ["--voices", "8192"] if workload == "nice_mix" else []
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "20", "--warmup", "5", "--workload", workload, "--dump-outputs", d] + extra,
+                           capture_output=True, text=True, timeout=280, env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = _last_json(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == (48 if workload == "nice_mix" else 20)
+        for key in ("repeats", "parity", "cpu_baseline", "config4", "config5_shard", "one_launch_per_step", "batched_launches"):
+            assert key not in line, key
+        dumps.append(np.load(os.path.join(d, "output.npy")))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == ((2, 1024) if workload == "nice_mix" else (1024, 4096))
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.abs(a).max() > 0
+    if workload == "pulseosc":
+        import ctypes as C
+        from oracle import pyoracle as po
+        from zang_amd import workloads
+        freq, color, _, _ = workloads.voice_params(2, 0, 4096)
+        L = po.lib()
+        for v in (0, 1, 777, 4095):
+            st = po.PulseOsc()
+            L.zo_pulseosc_init(C.byref(st))
+            ref = np.zeros(1024, np.float32)
+            for _ in range(20 + 5 + 20 + 20):
+                ref[:] = 0
+                L.zo_pulseosc_paint(C.byref(st), 0, 1024, po.fptr(ref), 48000.0, po.constant(float(freq[v])), float(color[v]))
+            assert np.array_equal(a[:, v].view(np.uint32), ref.view(np.uint32)), v

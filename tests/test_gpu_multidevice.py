@@ -93,7 +93,7 @@ def test_bench_two_ranks_preflight_and_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "ZH_BENCH_EMULATE")}
     r = subprocess.run([sys.executable, bench, "--gpus", "2", "--preflight"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "20", "--warmup", "5", "--voices", "16384"], capture_output=True, text=True, timeout=400, env=env)
+    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "20", "--warmup", "5", "--voices", "16384", "--full"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["collective"]["world_size_seen"] == 2 and "rccl" in d["collective"]["backend"]

@@ -10,7 +10,7 @@ from zang_amd import zscript_native as native
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SCRIPT = open(os.path.join(HERE, "golden", "script_modules.txt")).read()
-REF_SCRIPT = "/root/reference/examples/script.txt"
+REF_SCRIPT = os.path.join(HERE, "golden", "example_script.txt")      # the reference's examples/script.txt, as data
 
 
 def test_native_matches_reference_golden_text():
@@ -38,7 +38,6 @@ def test_native_equals_python_on_test_script():
         assert a == b and ma == mb and sorted(mb) == sorted(only)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SCRIPT), reason="the reference's example script only exists in the build container")
 def test_native_equals_python_on_reference_example_script():
     text = open(REF_SCRIPT).read()
     py, nat = _both(text)

@@ -6,8 +6,8 @@ mkdir -p $out
 cd $root
 commit=$(python3 -c "import json; print(json.load(open('zang_amd/build_info.json')).get('commit') or 'unknown')" 2>/dev/null || echo unknown)
 # 1. the driver's command line, five times
-for i in 1 2 3 4 5; do python bench.py --steps 20 --warmup 5 > $out/bench_driver_args_$i.json 2>/dev/null; done
-python bench.py > $out/bench_default.json 2>/dev/null
+for i in 1 2 3 4 5; do python bench.py --steps 20 --warmup 5 --full > $out/bench_driver_args_$i.json 2>/dev/null; done
+python bench.py --full > $out/bench_default.json 2>/dev/null
 # 2. rocprofv3 kernel statistics (profiled + unprofiled line per workload)
 p() { name=$1; shift; bash tools/prof_one.sh r05c $name "$@" > $out/prof_$name.txt 2>&1; }
 p pulseosc4096_driver_args --steps 20 --warmup 5

@@ -31,8 +31,8 @@ python tools/gen_song.py > /tmp/song.txt
 python tools/time_song.py /tmp/song.txt 60 2>&1 | grep -v amdgpu.ids > $out/song_60s.txt
 else
 # 5. the driver's command line, five times, and the default line
-for i in 1 2 3 4 5; do python bench.py --steps 20 --warmup 5 > $out/bench_driver_args_$i.json 2>/dev/null; done
-python bench.py > $out/bench_default.json 2>/dev/null
-python bench.py --workload noise_filter_fused --tolerant --steps 20 --warmup 5 > $out/bench_nf_tolerant_driver_args.json 2>/dev/null
+for i in 1 2 3 4 5; do python bench.py --steps 20 --warmup 5 --full > $out/bench_driver_args_$i.json 2>/dev/null; done
+python bench.py --full > $out/bench_default.json 2>/dev/null
+python bench.py --workload noise_filter_fused --tolerant --steps 20 --warmup 5 --full > $out/bench_nf_tolerant_driver_args.json 2>/dev/null
 fi
 ls $out

@@ -24,10 +24,11 @@ for round in 1 2 3; do
  done
 done
 echo "# rocprofv3 --kernel-trace --stats, the same form at --steps 20 --warmup 5 (per-kernel average without the inter-launch gaps)"
+root=$PWD
 cd /tmp && export TMPDIR=/tmp
 for v in "A=1" "ZH_FORMS=osc_fc=8" "ZH_BENCH_NO_TABLE=1"; do
   d=/tmp/r06pc_$$; rm -rf $d
-  env ZH_BENCH_IN_ORDER=1 $v rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu --no-config5 --no-parity --repeats 30 > /dev/null 2>&1
+  env ZH_BENCH_IN_ORDER=1 $v rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 $root/bench.py --steps 20 --warmup 5 --full --no-cpu --no-config5 --no-parity --repeats 30 > /dev/null 2>&1
   echo "## $v"; python3 -c "
 import csv, glob, sys
 for r in csv.DictReader(open(glob.glob('$d/*/*kernel_stats.csv')[0])):

@@ -5,7 +5,7 @@
 set -u
 O=gpurun_out/r06_pk; mkdir -p $O
 timeout 120 tools/ubench/pk_svf > $O/ubench_pk_svf.txt 2>&1; cat $O/ubench_pk_svf.txt
-us() { python bench.py "$@" --no-cpu --no-config4 --no-config5 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.2f us/step, parity %s' % (d['ms_per_step']*1e3, d.get('parity')))"; }
+us() { python bench.py "$@" --full --no-cpu --no-config4 --no-config5 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.2f us/step, parity %s' % (d['ms_per_step']*1e3, d.get('parity')))"; }
 {
 for round in 1 2 3; do
   echo -n "tree  noise_filter_fused 4096: "; us --workload noise_filter_fused --steps 200 --warmup 20

@@ -8,7 +8,7 @@ line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().split
 {
 echo "# config 3 tolerant, recorded pipelined (bench.py --workload noise_filter_fused --tolerant --steps 20 --warmup 5), three alternating rounds"
 for round in 1 2 3; do for fr in 0 64 128 256; do
-  echo -n "nf_tp_pipe_frames=$fr: "; ZH_FORMS=nf_tp_pipe_frames=$fr python bench.py --workload noise_filter_fused --tolerant --steps 20 --warmup 5 --no-cpu 2>/dev/null | line
+  echo -n "nf_tp_pipe_frames=$fr: "; ZH_FORMS=nf_tp_pipe_frames=$fr python bench.py --workload noise_filter_fused --tolerant --steps 20 --warmup 5 --full --no-cpu 2>/dev/null | line
 done; done
 } > $O/ab_nf_pipe_frames.txt 2>&1
 cat $O/ab_nf_pipe_frames.txt

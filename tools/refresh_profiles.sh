@@ -8,7 +8,7 @@ mkdir -p $out/ubench
 cd $root
 bash tools/bench_all.sh $tag > $out/bench_all.log 2>&1
 cp gpurun_out/bench_all_$tag/bench_unprofiled.jsonl gpurun_out/bench_all_$tag/song_60s.txt $out/
-python bench.py > $out/bench_default_with_cpu_baseline.json 2> /dev/null
+python bench.py --full > $out/bench_default_with_cpu_baseline.json 2> /dev/null
 bash tools/collect_profiles.sh $tag > $out/collect_profiles.log 2>&1
 cp gpurun_out/profiles_$tag/* $out/
 bash tools/collect_pmc_valu.sh $tag > $out/collect_pmc_valu.log 2>&1
