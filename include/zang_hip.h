@@ -177,11 +177,15 @@ ZH_API int  zh_graph_begin_capture(zh_ctx *ctx);
  * since * ifreq EXACTLY (`cnt +%= ifreq`, PulseOsc.zig:111, TriSawOsc.zig:115), so no paint needs the counters the previous
  * one left: consecutive paints of one module over the same span into images that do not overlap are recorded as ONE
  * launch of up to 32 buffers (exactly the launch zh_pulseosc_paint_batch makes: counters read once, written once).  When
- * something else is recorded, or the capture ends, what is held back goes out -- as two launches of half the buffers each
- * where one would leave the module's double-buffered counters on the other side (a replay then ends on the buffer it began
- * on and nothing has to be copied).  Replays give the same bits as a capture without the flag; what changes is that one
- * launch's ramp and tail are shared by the buffers.  Every other call first records what was held back, then itself, in
- * order as before.
+ * something else is recorded, or the capture ends, what is held back goes out.  A capture that recorded NOTHING but such
+ * oscillator batches (no other kernel, copy, memset or event, no side stream) is replayed directly: zh_graph_launch enqueues
+ * one launch per batch on the context's stream, as zh_pulseosc_paint_batch would -- it reads the live counters and flips, so
+ * the 20 paints of one capture are ONE launch of 20 buffers, and no host-side graph launch precedes it (form row
+ * `graph_direct`, 1 by default; 0 = always the recorded graph).  The recorded graph stays the fallback: in it the last batch is
+ * two launches of half the buffers each where one would leave the module's double-buffered counters on the other side (a
+ * replay then ends on the buffer it began on and nothing has to be copied); zh_graph_info describes that graph.  Replays give
+ * the same bits as a capture without the flag; what changes is that one launch's ramp and tail are shared by the buffers.
+ * Every other call first records what was held back, then itself, in order as before.
  * Also held back: zh_nice_paint_mix_stereo (flagged ZH_PAINT_TOLERANT only from 65,536 voices on).  Its paints DO depend on each other (the voices' state), so
  * they are not reordered: consecutive ones of one instrument over one span with the same gains into different mix rows become the
  * launch zh_nice_paint_mix_stereo_batch makes, up to 8 buffers each -- the state words stay in registers from buffer to buffer and
@@ -197,11 +201,12 @@ ZH_API int  zh_graph_begin_capture(zh_ctx *ctx);
  * branches on 2-4 forked streams -- kernels from different queues slow each other down, 5.0-5.6 against 4.5 us per buffer.) */
 enum { ZH_CAPTURE_COALESCE = 1 };
 ZH_API int  zh_graph_begin_capture_flags(zh_ctx *ctx, uint32_t flags);
-/* how a graph was recorded: nodes in it; paint calls that were held back while recording and the launches they became
- * (both 0 without ZH_CAPTURE_COALESCE) */
+/* how a graph was recorded: nodes in it; paint calls that were held back while recording and the launches they became in the
+ * recorded graph (both 0 without ZH_CAPTURE_COALESCE).  A direct replay (ZH_CAPTURE_COALESCE above) may make fewer: zh_graph_kernels */
 ZH_API int  zh_graph_info(const zh_graph *graph, uint32_t *nodes, uint32_t *paints_held, uint32_t *launches_of_held);
-/* the kernels a replay of the graph runs, in order of first launch while recording, with their counts: "k_osc_const4[batch] x2",
- * "k_nf_tp_a x1,k_nf_tp_ba x19,k_nf_tp_b x1" ([batch]: the instantiation that paints several buffers per launch).  What
+/* the kernels a replay of the graph runs, in order of first launch while recording, with their counts: "k_osc_const4[batch] x1"
+ * (20 paints, replayed directly; "x2" from the recorded graph), "k_nf_tp_a x1,k_nf_tp_ba x19,k_nf_tp_b x1" ([batch]: the
+ * instantiation that paints several buffers per launch).  What
  * bench.py's roofline record names: zh_last_form after a paint CALL says nothing about a paint that was held back. */
 ZH_API int  zh_graph_kernels(const zh_graph *graph, char *out, size_t n);
 ZH_API int  zh_graph_end_capture(zh_ctx *ctx, zh_graph **out);

@@ -1,7 +1,7 @@
 // hip_stub.cpp -- a HIP runtime that is not one: just enough of the API for the HOST side of libzang_hip.so to run on a box
 // without a GPU, under AddressSanitizer + UBSan (tools/host_asan.sh).  Memory is malloc'ed and tracked (a hipFree of a pointer
-// this stub never returned, or twice, aborts), streams know whether they are capturing, a captured "graph" counts its kernel
-// nodes, kernels are never run.  What is exercised is the library's own bookkeeping: capture logs, held-back batches, flips,
+// this stub never returned, or twice, aborts), streams know whether they are capturing, a captured "graph" counts its nodes and
+// knows their types (kernel, copy, memset), kernels are never run.  What is exercised is the library's own bookkeeping: capture logs, held-back batches, flips,
 // scratch growth and retirement, graph / module / context lifetimes.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -9,9 +9,10 @@
 #include <string.h>
 #include <map>
 #include <set>
+#include <vector>
 
 namespace {
-struct FakeGraph { unsigned nodes = 0; };
+struct FakeGraph { unsigned nodes = 0; std::vector<hipGraphNodeType> types; };   // (a node handle = the address of its entry in `types`)
 struct FakeExec { unsigned nodes = 0; };
 struct FakeStream { bool capturing = false; FakeGraph *g = nullptr; };
 struct FakeEvent { int x = 0; };
@@ -24,6 +25,7 @@ struct CallCfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
 thread_local CallCfg g_cfg[8];
 thread_local int g_cfg_n = 0;
 void die(const char *what) { fprintf(stderr, "hip_stub: %s\n", what); abort(); }
+void record(FakeStream *fs, hipGraphNodeType t) { fs->g->nodes++; fs->g->types.push_back(t); }
 FakeStream *S(hipStream_t s) {
     FakeStream *fs = reinterpret_cast<FakeStream *>(s);
     if (fs && !g_streams.count(fs)) die("a stream that does not exist (destroyed?)");
@@ -73,7 +75,25 @@ hipError_t hipStreamEndCapture(hipStream_t s, hipGraph_t *g) {
     return hipSuccess;
 }
 hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus *st) { FakeStream *fs = S(s); *st = fs && fs->capturing ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone; return hipSuccess; }
-hipError_t hipGraphGetNodes(hipGraph_t g, hipGraphNode_t *, size_t *n) { FakeGraph *fg = reinterpret_cast<FakeGraph *>(g); if (!g_graphs.count(fg)) die("hipGraphGetNodes: dead graph"); *n = fg->nodes; return hipSuccess; }
+hipError_t hipGraphGetNodes(hipGraph_t g, hipGraphNode_t *nodes, size_t *n) {
+    FakeGraph *fg = reinterpret_cast<FakeGraph *>(g);
+    if (!g_graphs.count(fg)) die("hipGraphGetNodes: dead graph");
+    if (nodes) {
+        if (*n < fg->nodes) die("hipGraphGetNodes: array shorter than the graph");
+        for (unsigned i = 0; i < fg->nodes; i++) nodes[i] = reinterpret_cast<hipGraphNode_t>(&fg->types[i]);
+    }
+    *n = fg->nodes;
+    return hipSuccess;
+}
+hipError_t hipGraphNodeGetType(hipGraphNode_t node, hipGraphNodeType *t) {
+    for (FakeGraph *fg : g_graphs)
+        if (!fg->types.empty() && (const void *)node >= (const void *)fg->types.data() && (const void *)node < (const void *)(fg->types.data() + fg->types.size())) {
+            *t = *reinterpret_cast<const hipGraphNodeType *>(node);
+            return hipSuccess;
+        }
+    die("hipGraphNodeGetType: not a node of a live graph");
+    return hipErrorInvalidValue;
+}
 hipError_t hipGraphInstantiate(hipGraphExec_t *e, hipGraph_t g, hipGraphNode_t *, char *, size_t) {
     FakeGraph *fg = reinterpret_cast<FakeGraph *>(g);
     if (!g_graphs.count(fg)) die("hipGraphInstantiate: dead graph");
@@ -88,7 +108,7 @@ static hipError_t copy_like(void *dst, const void *src, size_t n, hipMemcpyKind 
     const bool dev_dst = kind == hipMemcpyHostToDevice || kind == hipMemcpyDeviceToDevice, dev_src = kind == hipMemcpyDeviceToHost || kind == hipMemcpyDeviceToDevice;
     if (n && dev_dst && !known(dst, n)) die("a copy into device memory that is not (any more) allocated, or past its end");
     if (n && dev_src && !known(src, n)) die("a copy from device memory that is not (any more) allocated, or past its end");
-    if (fs && fs->capturing) { fs->g->nodes++; return hipSuccess; }   // recorded, not run
+    if (fs && fs->capturing) { record(fs, hipGraphNodeTypeMemcpy); return hipSuccess; }   // recorded, not run
     if (n) memmove(dst, src, n);
     return hipSuccess;
 }
@@ -101,7 +121,7 @@ hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t sp
 hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t s) {
     FakeStream *fs = S(s);
     if (n && !known(dst, n)) die("hipMemsetAsync outside a live allocation");
-    if (fs && fs->capturing) { fs->g->nodes++; return hipSuccess; }
+    if (fs && fs->capturing) { record(fs, hipGraphNodeTypeMemset); return hipSuccess; }
     memset(dst, v, n);
     return hipSuccess;
 }
@@ -116,7 +136,7 @@ hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *shmem, hip
 hipError_t hipLaunchKernel(const void *, dim3 grid, dim3 block, void **, size_t, hipStream_t s) {
     if (!grid.x || !grid.y || !grid.z || !block.x || block.x * block.y * block.z > 1024 || grid.y > 65535 || grid.z > 65535) die("a kernel launch with an impossible grid or block");
     FakeStream *fs = S(s);
-    if (fs && fs->capturing) { fs->g->nodes++; g_captured++; } else g_launches++;
+    if (fs && fs->capturing) { record(fs, hipGraphNodeTypeKernel); g_captured++; } else g_launches++;
     return hipSuccess;
 }
 void **__hipRegisterFatBinary(const void *) { static void *h; return &h; }

@@ -52,6 +52,18 @@ struct zh_co_batch {             // the paints held back: same module, span, fla
     std::vector<float *> imgs;
     std::shared_ptr<void> items;  // what else the owner keeps per held paint (composite.hip: the mixdowns' params)
     std::function<void(hipStream_t, float *const *, uint32_t)> launch;
+    // the kernel one launch of the batch runs, set by owners whose launch reads everything it needs from the module's state AS IT IS
+    // when the launch is made (the oscillators: the live counter buffer, then a flip): such a batch may be replayed by calling
+    // `launch` again instead of through the recorded graph (zh_direct_item).  nullptr: the recorded graph only
+    const char *kernel = nullptr;
+};
+// One held-back batch of a ZH_CAPTURE_COALESCE capture, kept for a DIRECT replay (ctx.hip zh_graph_launch): a capture whose recorded
+// work is nothing but such batches is replayed by enqueuing their launches on the context's stream again, one per item, each reading
+// the live counters and flipping once -- what the eager batch path does.  No buffer has to be reconciled, so an item is never split.
+struct zh_direct_item {
+    std::function<void(hipStream_t, float *const *, uint32_t)> launch;
+    std::vector<float *> imgs;
+    const char *kernel;
 };
 
 struct zh_ctx {
@@ -80,6 +92,11 @@ struct zh_ctx {
     // the first error of a launch that a ZH_CAPTURE_COALESCE capture made on a held-back paint's behalf, after the paint call itself
     // had returned ZH_OK: zh_graph_end_capture returns it instead of a graph that lacks those paints
     int deferred_error = 0;
+    // the direct replay plan of the capture that is recording (zh_direct_item): its held-back batches in order; the kernel launches
+    // the capture recorded (zh_note_launch) and how many of them the batches of the plan made -- the plan is kept only if they agree
+    std::vector<zh_direct_item> co_plan;
+    bool co_plan_ok = true;
+    uint32_t capture_launches = 0, co_plan_launches = 0;
     void *noise_jump;            // xoshiro256++ jump tables (noise_jump.hip), built on first use, freed with the context
 };
 
@@ -91,6 +108,9 @@ struct zh_graph {
     uint32_t nodes = 0;          // nodes of the recorded graph
     uint32_t co_paints = 0, co_launches = 0;   // ZH_CAPTURE_COALESCE: paint calls held back while recording, launches they became
     std::vector<std::pair<std::string, uint32_t>> kernels;   // zh_ctx::capture_kernels of the capture
+    // the direct replay plan (empty: the capture recorded something else; replays go through `exec`) and the kernels it launches
+    std::vector<zh_direct_item> plan;
+    std::vector<std::pair<std::string, uint32_t>> plan_kernels;
 };
 
 // Every entry point that allocates or launches runs with the context's device current and restores the caller's
@@ -139,7 +159,7 @@ enum { ZF_SINE_RANGES, ZF_NOISE_RANGES, ZF_ENVELOPE_RANGES, ZF_SAMPLER_RANGES, Z
        ZF_SCRIPT_RANGES, ZF_SCRIPT_RANGES_MAXV, ZF_OSC_FC, ZF_NICE_PC_MAX, ZF_NICE_PC4_MAX, ZF_NICE_WAVE_MAX, ZF_PMOSC_WAVE_MAX,
        ZF_NICE_MIX_ROLL, ZF_NICE_MIX_WG_MIN, ZF_NF_PC_MAX, ZF_NF_RING_MAX, ZF_FILTER_PC_MAX, ZF_FILTER_PC16_MAX, ZF_FILTER_PC_CTL_MAX,
        ZF_PINK_PIPE_MAX, ZF_PINK_TAPS, ZF_ECHOES_PC_MAX, ZF_DELAY_FRAMES_MAX, ZF_FILTER_TP_MAX, ZF_NF_TP_MAX, ZF_NICE_TP_MAX,
-       ZF_PINK_TP_MAX, ZF_ECHOES_TP_MAX, ZF_NICE_MIX_FMA, ZF_BASICS_ROWS_MIN, ZF_SCRIPT_PC, ZF_SCRIPT_PC_MAXV, ZF_NF_TP_PIPE_FRAMES, ZF_DISTORTION_ROWS_MIN, ZF_DISTORTION_RC, ZF_COUNT };
+       ZF_PINK_TP_MAX, ZF_ECHOES_TP_MAX, ZF_NICE_MIX_FMA, ZF_BASICS_ROWS_MIN, ZF_SCRIPT_PC, ZF_SCRIPT_PC_MAXV, ZF_NF_TP_PIPE_FRAMES, ZF_DISTORTION_ROWS_MIN, ZF_DISTORTION_RC, ZF_GRAPH_DIRECT, ZF_COUNT };
 long zh_form(int id);
 bool zh_form_is_set(int id);                 // the row is overridden through ZH_FORMS
 uint32_t zh_range_frames(uint32_t V, uint32_t n, int form, uint32_t target_waves, uint32_t max_voices);

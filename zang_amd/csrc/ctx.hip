@@ -48,6 +48,10 @@ void zh_epoch_flush_batch(zh_ctx *c, bool last) {
     uint32_t flips = 0;
     for (const zh_flip_use &u : c->capture_log)
         if ((const void *)u.f == b.owner) flips = u.flips;
+    // the direct replay plan keeps the batch whole (zh_graph_launch: it flips the live counters, nothing to reconcile)
+    if (b.kernel) c->co_plan.push_back(zh_direct_item{b.launch, b.imgs, b.kernel});
+    else c->co_plan_ok = false;
+    const uint32_t before = c->co_launches;
     if (b.flips && last && n >= 2 && ((flips + 1u) & 1u)) {              // one launch would leave an odd number of flips: two halves instead
         const uint32_t h = n / 2;
         c->co_launches += 2;
@@ -57,9 +61,11 @@ void zh_epoch_flush_batch(zh_ctx *c, bool last) {
         c->co_launches++;
         b.launch(c->stream, b.imgs.data(), n);
     }
+    if (b.kernel) c->co_plan_launches += c->co_launches - before;
     b.imgs.clear();
     b.items.reset();
     b.launch = nullptr;
+    b.kernel = nullptr;
 }
 void zh_epoch_barrier(zh_ctx *c) {
     if (!c->epoch_open) return;
@@ -261,6 +267,8 @@ int zh_graph_begin_capture_flags(zh_ctx *ctx, uint32_t flags) { ZH_GUARD(ctx);
     ctx->co_paints = ctx->co_launches = 0;
     ctx->capture_kernels.clear();
     ctx->deferred_error = 0;
+    ctx->co_plan.clear(); ctx->co_plan_ok = true;
+    ctx->capture_launches = ctx->co_plan_launches = 0;
     return ZH_OK;
 }
 int zh_graph_begin_capture(zh_ctx *ctx) { return zh_graph_begin_capture_flags(ctx, 0); }
@@ -282,6 +290,9 @@ int zh_graph_end_capture(zh_ctx *ctx, zh_graph **out) { ZH_GUARD(ctx);
             if (it != g_flippers.end()) it->second->cur = u.first_cur;
         }
     }
+    std::vector<zh_direct_item> plan;
+    plan.swap(ctx->co_plan);
+    const bool plan_ok = ctx->co_plan_ok && !plan.empty() && ctx->capture_launches == ctx->co_plan_launches;
     ZH_TRY(hipStreamEndCapture(ctx->stream, &g));
     if (ctx->deferred_error) {                                // a held-back paint failed when it was finally launched: no graph
         const int rc = ctx->deferred_error;
@@ -304,13 +315,51 @@ int zh_graph_end_capture(zh_ctx *ctx, zh_graph **out) { ZH_GUARD(ctx);
     zg->kernels.swap(ctx->capture_kernels);
     size_t nn = 0;
     if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess) zg->nodes = (uint32_t)nn;
+    // The direct replay plan stands in for the graph only if the graph holds exactly the plan's launches: every kernel the capture
+    // launched came from a held-back oscillator batch (ctx->capture_launches), and the graph has that many nodes, all of them kernels --
+    // no copy, memset or event node, no work of a side stream, nothing enqueued on the stream by anyone else.
+    if (plan_ok && nn == ctx->co_plan_launches) {
+        std::vector<hipGraphNode_t> nodes(nn);
+        bool kernels_only = hipGraphGetNodes(g, nodes.data(), &nn) == hipSuccess && nn == nodes.size();
+        for (size_t i = 0; kernels_only && i < nn; i++) {
+            hipGraphNodeType t;
+            kernels_only = hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel;
+        }
+        if (kernels_only) {
+            for (const zh_direct_item &it : plan) {                  // what a direct replay launches (zh_graph_kernels)
+                const std::string key = std::string(it.kernel) + (it.imgs.size() > 1 ? "[batch]" : "");
+                bool found = false;
+                for (auto &kv : zg->plan_kernels) if (kv.first == key) { kv.second++; found = true; break; }
+                if (!found) zg->plan_kernels.emplace_back(key, 1u);
+            }
+            zg->plan.swap(plan);
+        }
+    }
     (void)hipGetLastError();
     *out = zg;
     return ZH_OK;
 }
 
+// a direct replay is taken (zh_graph_launch) and reported (zh_graph_kernels) when the graph has a plan and the form table allows it
+static bool zh_graph_direct(const zh_graph *graph) { return !graph->plan.empty() && zh_form(ZF_GRAPH_DIRECT) != 0; }
+
 int zh_graph_launch(zh_ctx *ctx, zh_graph *graph) { ZH_GUARD(ctx);
     if (!ctx || !graph || ctx->capturing || graph->ctx != ctx) return ZH_ERR_INVALID;     // (graph->ctx is null once its context was destroyed)
+    if (zh_graph_direct(graph)) {
+        // The recorded work was nothing but held-back oscillator batches: enqueue each as the eager batch path does -- it reads the
+        // live counters, writes the other buffer and flips -- with no host-side graph launch, no reconciliation copy, and one
+        // launch per batch where the recorded graph may hold two.
+        {
+            std::lock_guard<std::mutex> lk(g_flip_mu);
+            for (const zh_flip_use &u : graph->flips)
+                if (g_flippers.find(u.id) == g_flippers.end()) return ZH_ERR_INVALID;     // module destroyed since the capture
+        }
+        zh_ctx *const tls = zh_tls_ctx;
+        zh_tls_ctx = nullptr;                                 // (a replay is not a paint call: zh_last_form stays, as under hipGraphLaunch)
+        for (const zh_direct_item &it : graph->plan) it.launch(ctx->stream, it.imgs.data(), (uint32_t)it.imgs.size());
+        zh_tls_ctx = tls;
+        return zh_launch_status();
+    }
     // A replay reads each chunked oscillator's phase counters from the buffer the capture started on.  Paints since
     // then (eager ones, or another graph with an odd number of them) may have left the live state in the other
     // buffer: copy it over first (n * 4 bytes, enqueued ahead of the replay), then account for the replay's flips.
@@ -342,7 +391,7 @@ int zh_graph_info(const zh_graph *graph, uint32_t *nodes, uint32_t *paints_held,
 int zh_graph_kernels(const zh_graph *graph, char *out, size_t n) {
     if (!graph || !out || n == 0) return ZH_ERR_INVALID;
     std::string s;
-    for (const auto &kv : graph->kernels) {
+    for (const auto &kv : zh_graph_direct(graph) ? graph->plan_kernels : graph->kernels) {
         if (!s.empty()) s += ',';
         s += kv.first + " x" + std::to_string(kv.second);
     }

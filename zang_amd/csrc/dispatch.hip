@@ -63,6 +63,7 @@ const FormRow kForms[ZF_COUNT] = {
     /* ZF_NF_TP_PIPE_FRAMES  */ {"nf_tp_pipe_frames", 0, "ZH_PAINT_TOLERANT Noise -> Filter voice recorded pipelined (ZH_CAPTURE_COALESCE, k_nf_tp_ba): frames per chunk, a multiple of 32; 0 = as outside a pipeline (32 at 4,096 voices)"},
     /* ZF_DISTORTION_ROWS_MIN */ {"distortion_rows_min", 32768, "Distortion clip: from here four voices per lane, three consecutive rows of a 256-voice column per wave, the per-voice constants once per workgroup through LDS (k_distortion_chunks: 224 -> 178 us at 131,072 voices); the overdrive too when this row is set by hand (no faster: 239 against 244-250 us)"},
     /* ZF_DISTORTION_RC      */ {"distortion_rc", 0, "... rows per wave of that form: 3 (0), 6 or 8"},
+    /* ZF_GRAPH_DIRECT       */ {"graph_direct", 1, "zh_graph_launch of a ZH_CAPTURE_COALESCE capture that recorded nothing but held-back oscillator batches: 1 = their launches enqueued directly, one per batch of up to 32 buffers (20 paints: one launch of 20), 0 = the recorded hipGraph (20 paints: two launches of 10)"},
 };
 
 struct Overrides { bool set[ZF_COUNT]; long val[ZF_COUNT]; };
@@ -123,6 +124,7 @@ void zh_note_launch(zh_ctx *ctx, const char *kernel) {
     zh_tls_launch_detail = nullptr;
     if (!ctx) return;
     if (ctx->capturing) {                                     // the capture's own list: every launch counted, the detail kept
+        ctx->capture_launches++;
         const char *b0 = kernel;
         while (*b0 == '(' || *b0 == ' ') b0++;
         size_t n0 = 0;

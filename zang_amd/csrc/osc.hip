@@ -530,9 +530,11 @@ static void launch_osc_const(M *m, const zh_buf *outs, uint32_t nb, uint32_t sta
         // zh_*_paint_batch launches: the phase of frame i of buffer b is cnt0 + (b * frames + i) * ifreq, the counters are read
         // from cnt[cur] and written to the other buffer once, and the module flips once per launch.  When the epoch ends
         // (zh_epoch_barrier: another call on the context, or the end of the capture) the last batch is recorded as TWO launches of
-        // half the buffers each if one launch would leave the capture with an odd number of flips: a replay then ends on the
-        // buffer it started from and zh_graph_launch has no counters to copy (an odd count costs a 16 KiB copy per replay; a
-        // separate publish node cost 4.4 us of a 61 us replay in the first version of this path).
+        // half the buffers each if one launch would leave the capture with an odd number of flips: a replay of the recorded graph
+        // then ends on the buffer it started from and zh_graph_launch has no counters to copy (an odd count costs a 16 KiB copy per
+        // replay; a separate publish node cost 4.4 us of a 61 us replay in the first version of this path).  A capture of nothing but
+        // such batches is replayed DIRECTLY instead (cb.kernel; ctx.hip zh_graph_launch): the closure below is called again per
+        // batch, reads the live counters and flips, so the batch is never split there -- 20 paints are one launch of 20.
         if (use_tab && ctx->capturing && (ctx->capture_flags & ZH_CAPTURE_COALESCE)) {
             const uint32_t key = (zf ? 1u : 0u) | ((uint32_t)sm << 1) | ((uint32_t)fc << 8);
             for (uint32_t b = 0; b < nb; b++) {
@@ -547,6 +549,7 @@ static void launch_osc_const(M *m, const zh_buf *outs, uint32_t nb, uint32_t sta
                 if (!join) {
                     zh_epoch_flush_batch(ctx, false);
                     cb.active = true; cb.owner = m; cb.start = start; cb.end = end; cb.stride = outs[b].stride; cb.key = key; cb.flips = true;
+                    cb.kernel = "k_osc_const4";
                     ctx->epoch_open = true;
                     const OscArgs ab = a;
                     cb.launch = [ab, launch, m](hipStream_t s2, float *const *imgs, uint32_t cnt) {
