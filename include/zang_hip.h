@@ -699,6 +699,34 @@ ZH_API int zh_script_module_get_state(zh_script_module *m, uint32_t *host_words)
 ZH_API int zh_script_module_set_state(zh_script_module *m, const uint32_t *host_words);
 ZH_API int zh_script_module_paint(zh_script_module *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
                                   zh_bool note_id_changed, const zh_script_param *params, uint32_t n_params, uint32_t flags);
+/* Per-voice sub-spans of a generated module for one buffer: what NoteTracker -> PolyphonyDispatcher -> Trigger yields
+ * (examples/example_script_runtime_poly.zig:146-164).  Device arrays [span_index][voice], like zh_span_table. */
+typedef struct zh_script_span_table {
+    uint32_t max_spans, reserved;
+    const uint32_t *count;            /* [n_voices]                 */
+    const uint32_t *start, *end;      /* [max_spans][n_voices]      */
+    const uint8_t  *note_id_changed;  /* [max_spans][n_voices]      */
+} zh_script_span_table;
+/* Per-sub-span values of param i ([max_spans][n_voices] device arrays).  Both NULL: params[i] holds for every sub-span. */
+typedef struct zh_script_span_param {
+    const float    *f;   /* ZH_SP_CONSTANT, the constant of a ZH_SP_COB, the f32 payload of a ZH_SP_ENUM */
+    const uint32_t *u;   /* ZH_SP_BOOLEAN (0/1), the index of a ZH_SP_ENUM */
+} zh_script_span_param;
+/* zh_zscript_generate_hip_forms: next to zs_paint_<name>, zs_paint_spans_<name> (zh_script_module_paint_spans) */
+#define ZH_ZSCRIPT_FORM_SPANS 8
+/* One launch does, for every voice v, the reference's sequence of paint(sub_span_k, outputs, temps, note_id_changed[k][v],
+ * params_k) calls for k < min(count[v], max_spans), each call's prologue and epilogue included, empty sub-spans (start == end)
+ * at any position too.  Sub-spans of a voice are ascending and non-overlapping inside [span_start, span_end]; a sub-span that
+ * starts before the previous one ends, or before span_start, is never reached and ends the voice's list.  Frames of a voice
+ * that no sub-span covers are left as they are; with ZH_PAINT_ZERO_FIRST every frame of [span_start, span_end) is written, 0
+ * where nothing paints.  params[i] keeps its zh_script_module_paint meaning wherever span_params[i] (host array [n_params], or
+ * NULL for none) gives no array; waveform images and cob images stay indexed by absolute frame, curves stay shared.
+ * ZH_ERR_UNSUPPORTED: the module was generated without ZH_ZSCRIPT_FORM_SPANS, or ZH_PAINT_TOLERANT is set (the form is exact
+ * only).  ZH_ERR_INVALID: a span array on a BUFFER or CURVE param or on a COB param whose is_buffer is set, `u` on a CONSTANT or
+ * COB, `f` on a BOOLEAN, a NULL table array, max_spans == 0.  No voices: ZH_OK, nothing runs.  Capturable (no host sync). */
+ZH_API int zh_script_module_paint_spans(zh_script_module *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
+                                        const zh_script_param *params, uint32_t n_params, const zh_script_span_param *span_params,
+                                        const zh_script_span_table *table, uint32_t flags);
 
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text

@@ -53,6 +53,7 @@ HOST_MODULES = ["sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
 # pointer parameters that address MANY elements (everything else of struct type points at one)
 MANY_NAMES = {"outputs", "temps", "host", "filter", "impulses"}
 MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_dispatch", "out"),
+                ("zh_script_module_paint_spans", "params"), ("zh_script_module_paint_spans", "span_params"),
                 # the batch call reads n_buffers elements of each
                 ("zh_nice_paint_mix_stereo_batch", "note_id_changed"), ("zh_nice_paint_mix_stereo_batch", "params")}
 # scalar pointer parameters that are a single out value, not an array

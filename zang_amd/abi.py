@@ -150,6 +150,17 @@ SP_CONSTANT, SP_BOOLEAN, SP_COB, SP_BUFFER, SP_ENUM, SP_CURVE = range(6)
 SCRIPT_MAX_PARAMS = 16
 
 
+class ScriptSpanTable(C.Structure):        # zh_script_span_table
+    _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("note_id_changed", vp)]
+
+
+class ScriptSpanParam(C.Structure):        # zh_script_span_param
+    _fields_ = [("f", vp), ("u", vp)]
+
+
+ZSCRIPT_FORM_SPANS = 8
+
+
 class CurveNode(C.Structure):
     _fields_ = [("value", f32), ("t", f32)]
 
@@ -413,6 +424,7 @@ SIGNATURES = {
     "zh_script_module_get_state": (C.c_int, [vp, vp]),
     "zh_script_module_set_state": (C.c_int, [vp, vp]),
     "zh_script_module_paint": (C.c_int, [vp, u32, u32, P(Buf), Bool, P(ScriptParam), u32, u32]),
+    "zh_script_module_paint_spans": (C.c_int, [vp, u32, u32, P(Buf), P(ScriptParam), u32, P(ScriptSpanParam), P(ScriptSpanTable), u32]),
     "zh_nice_create": (C.c_int, [vp, u32, F32, P(vp)]),
     "zh_nice_destroy": (C.c_int, [vp]),
     "zh_nice_get_state": (C.c_int, [vp, vp]),

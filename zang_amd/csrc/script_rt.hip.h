@@ -30,6 +30,12 @@ struct ZsLaunch {
     zh_script_param p[ZH_SCRIPT_MAX_PARAMS];
 };
 
+// zs_paint_spans_<name>'s second argument (zh_script_module_paint_spans): the voices' sub-spans and the per-sub-span param arrays
+struct ZsSpans {
+    zh_script_span_table t;
+    zh_script_span_param p[ZH_SCRIPT_MAX_PARAMS];
+};
+
 // frames per range of a launch with `ranges` = gridDim.y > 1 frame ranges over n frames (the loader picks `ranges` so that
 // this reproduces the length it planned with, script.hip)
 __host__ __device__ inline uint32_t zs_range_frames(uint32_t n, uint32_t ranges) { return ((n + ranges - 1) / ranges + 7) / 8 * 8; }
@@ -217,6 +223,64 @@ __device__ __forceinline__ void zs_frame_loop(float *__restrict__ out, uint32_t 
                                               const size_t *istride, const uint32_t *ivoff, uint32_t start, uint32_t end, bool zf, bool &walk, F &&f) {
     zs_frame_loop<CH, NIN>(out, v, ostride, in, istride, ivoff, start, end, zf, walk, f, [](int) { return false; }, f);
 }
+// ---- the per-voice sub-span form of a generated kernel (zs_paint_spans_<name>, zh_script_module_paint_spans) ---------------
+// a param's value for the sub-span at [k][v] (index k * V + v): the span array where there is one, else the paint's own value
+__device__ __forceinline__ float zs_span_f(const zh_script_param &p, const zh_script_span_param &s, size_t kv, uint32_t v) { return s.f ? s.f[kv] : zs_const(p, v); }
+__device__ __forceinline__ bool zs_span_b(const zh_script_param &p, const zh_script_span_param &s, size_t kv, uint32_t v) { return s.u ? s.u[kv] != 0 : zs_bool(p, v); }
+__device__ __forceinline__ uint32_t zs_span_tag(const zh_script_param &p, const zh_script_span_param &s, size_t kv) { return s.u ? s.u[kv] : p.u; }
+__device__ __forceinline__ float zs_span_payload(const zh_script_param &p, const zh_script_span_param &s, size_t kv) { return s.f ? s.f[kv] : p.f; }
+
+// The walk of composite.hip span_walk over a script module's frame loop: one lane per voice, and the wave walks the buffer in
+// segments that end at the next sub-span boundary of ANY of its lanes (a wave-wide minimum over all 64 lanes, taken before any
+// divergent branch).  Inside a segment no lane starts or ends a sub-span: the lanes inside one run zs_frame_loop over it, the
+// others store zeros (ZH_PAINT_ZERO_FIRST) or nothing.  begin(kv) runs the module's per-paint prologue for the lane's sub-span
+// at [k][v] at its first frame -- with only the lanes that start one there active, so a wave vote in a prologue (TriSawOscLane's
+// all_saw) speaks for those lanes, which is all the lanes that hold it read it for -- and end() its epilogue after its last.
+// `live`: the lane owns a voice (a lane past the last voice walks with no sub-spans and stores nothing).
+template <int CH, int NIN, class B, class E, class F, class Q, class FQ>
+__device__ __forceinline__ void zs_span_walk(const ZsLaunch &L, const ZsSpans &S, uint32_t v, bool live, const float *const *in, const size_t *istride,
+                                             const uint32_t *ivoff, bool &walk, B &&begin, E &&end_fn, F &&f, Q &&quiet, FQ &&fq) {
+    const uint32_t V = L.V;
+    const bool zf = (L.flags & ZH_PAINT_ZERO_FIRST) != 0;
+    const uint32_t cnt = live ? min(S.t.count[v], S.t.max_spans) : 0u;
+    uint32_t k = 0, cur_end = 0;
+    uint32_t next_start = cnt > 0 ? S.t.start[v] : 0xffffffffu;
+    bool active = false;
+    auto advance = [&](uint32_t i) ZH_INLINE_LAMBDA {
+        for (;;) {
+            if (active) {
+                if (i != cur_end) break;
+                end_fn();
+                active = false;
+                k++;
+                next_start = k < cnt ? S.t.start[(size_t)k * V + v] : 0xffffffffu;
+                continue;
+            }
+            if (i != next_start) break;
+            const size_t kv = (size_t)k * V + v;
+            cur_end = S.t.end[kv];
+            begin(kv);
+            active = true;
+        }
+    };
+    uint32_t i = L.start;
+    while (i < L.end) {
+        advance(i);                                             // sub-spans that end / begin at frame i
+        uint32_t ev = active ? cur_end : next_start;            // this lane's next boundary (> i)
+        ev = (ev > i && ev < L.end) ? ev : L.end;               // unsorted / out-of-range entries never fire
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ev = min(ev, (uint32_t)__shfl_xor((int)ev, off));
+        const uint32_t seg_end = __builtin_amdgcn_readfirstlane(ev);
+        if (active) {
+            zs_frame_loop<CH, NIN>(L.out, v, L.ostride, in, istride, ivoff, i, seg_end, zf, walk, f, quiet, fq);
+        } else if (zf && live) {
+            for (uint32_t j = i; j < seg_end; j++) zrow_store<1>(zrow_rsrc(L.out, L.ostride, j), v * 4u, 0, 0.0f);
+        }
+        i = seg_end;
+    }
+    advance(L.end);            // a sub-span that ends with the buffer; empty sub-spans at its end
+}
+
 // ---- the role-wave form of a generated kernel (zs_paint_pc_<name>; zscript_emit.hip plan_roles) -------------------------
 // Few voices: one workgroup of several waves owns 64 voices, and the frame body's units (builtin modules, arithmetic)
 // are dealt to ROLES -- waves that each run their own part of every frame and hand values on through LDS tiles, float4 =

@@ -391,6 +391,10 @@ struct Kernel {
     std::string name;
     std::vector<HipParam> params;
     Lines pro, frame, epi_ends, epi_stores;
+    // the spans form (zs_paint_spans_<name>) runs a paint's prologue once per sub-span: the lines of `pro` that belong to it (the
+    // top-level begin sink's), and the lines it splits into a declaration (once) and an assignment (per sub-span)
+    std::set<size_t> pro_begin;
+    std::map<size_t, std::pair<std::string, std::string>> pro_split;
     std::vector<Unit> units;       // the frame body again, unit by unit (k.frame == the units' texts in order)
     Mark mark() const { return Mark{epi_ends.size(), epi_stores.size(), quiet_terms.size(), units.size(), frame.size()}; }
     void unit_done(const Mark &m, Unit u) {
@@ -462,6 +466,15 @@ struct ModuleCtx {
         return n;
     }
     std::string fname(size_t i) const { return prefix + "f" + std::to_string(i); }
+};
+
+// what runs at a paint's first frame: ModuleCtx::begin_sink, with the top-level sink's lines marked for the spans form
+struct BeginSink {
+    ModuleCtx &mc;
+    void push_back(const std::string &l) const {
+        if (mc.begin_sink == &mc.k.pro) mc.k.pro_begin.insert(mc.k.pro.size());
+        mc.begin_sink->push_back(l);
+    }
 };
 
 // The sine placeholders of a frame-body line (call_builtin's SineOsc, instruction()'s sin) as code, now that the kernel's sinks are
@@ -610,7 +623,8 @@ public:
         }
         const std::string o = k.fresh("m");
         const size_t w = k.alloc(state_words(name));
-        Lines &decl = k.pro, &pro = *mc.begin_sink, &ends = *mc.end_sink, &epi = k.epi_stores;
+        Lines &decl = k.pro, &ends = *mc.end_sink, &epi = k.epi_stores;
+        const BeginSink pro{mc};
         Lines frame;
         std::string painted, value;
         const char *oc = o.c_str();
@@ -882,6 +896,7 @@ public:
         case IK::arith_float: case IK::arith_float_float: {
             const std::string expr = ins.kind == IK::arith_float ? un(ins.op, val(mc, ins.a).expr) : bin(ins.op, val(mc, ins.a).expr, val(mc, ins.b).expr);
             if (mc.begin_sink == &k.pro) {
+                k.pro_split[k.pro.size()] = {"float " + mc.fname(ins.out_float) + " = 0.0f;", mc.fname(ins.out_float) + " = " + expr + ";"};
                 k.pro.push_back("const float " + mc.fname(ins.out_float) + " = " + expr + ";");
             } else {                   // inside a delay / track body: evaluated once per chunk, like the Zig `const` in the loop
                 k.pro.push_back("float " + mc.fname(ins.out_float) + " = 0.0f;");
@@ -1046,8 +1061,8 @@ public:
         k.pro.push_back(strf("%s.next = zs_ld_u(L.state, %zu, V, v); %s.t = zs_ld_f(L.state, %zu, V, v); %s.cur = zs_ld_u(L.state, %zu, V, v);", tc, w, tc, w + 1, tc, w + 2));
         k.pro.push_back(strf("uint32_t %s_k = 0u, %s_note = 0u; bool %s_new = false;", tc, tc, tc));
         k.epi_stores.push_back(strf("zs_st_u(L.state, %zu, V, v, %s.next); zs_st_f(L.state, %zu, V, v, %s.t); zs_st_u(L.state, %zu, V, v, %s.cur);", w, tc, w + 1, tc, w + 2, tc));
-        mc.begin_sink->push_back(t + strf(".begin(zs_track%zu_t, %zuu, (", ti, track.notes.size()) + mc.env[0].expr + ") / (" + val(mc, ins.speed).expr + "), " + mc.length + ", " + reset + ");");
-        mc.begin_sink->push_back(t + "_k = 0u;");
+        BeginSink{mc}.push_back(t + strf(".begin(zs_track%zu_t, %zuu, (", ti, track.notes.size()) + mc.env[0].expr + ") / (" + val(mc, ins.speed).expr + "), " + mc.length + ", " + reset + ");");
+        BeginSink{mc}.push_back(t + "_k = 0u;");
         Lines begins, ends, body;
         Lines *sb = mc.begin_sink, *se = mc.end_sink;
         const std::string srel = mc.rel, slen = mc.length, snic = mc.nic;
@@ -1144,11 +1159,13 @@ public:
             switch (p.type.kind) {
             case PK::constant:
                 kind = "constant";
+                k.pro_split[k.pro.size()] = {strf("float P%zu = 0.0f;", i), strf("P%zu = zs_span_f(L.p[%zu], S.p[%zu], zs_kv, v);", i, i, i)};
                 k.pro.push_back(strf("const float P%zu = zs_const(L.p[%zu], v);", i, i));
                 v.kind = Val::flt; v.expr = strf("P%zu", i);
                 break;
             case PK::boolean:
                 kind = "boolean";
+                k.pro_split[k.pro.size()] = {strf("bool P%zu = false;", i), strf("P%zu = zs_span_b(L.p[%zu], S.p[%zu], zs_kv, v);", i, i, i)};
                 k.pro.push_back(strf("const bool P%zu = zs_bool(L.p[%zu], v);", i, i));
                 v.kind = Val::boolean; v.expr = strf("P%zu", i);
                 break;
@@ -1163,6 +1180,9 @@ public:
                 kind = "constant_or_buffer";
                 const size_t j = k.rows.size();
                 k.rows.push_back(i);
+                // (the spans form: is_buffer stays the paint's, as the input rows do; the constant may vary per sub-span)
+                k.pro_split[k.pro.size()] = {strf("const bool P%zu_b = L.p[%zu].is_buffer != 0; float P%zu_c = 0.0f;", i, i, i),
+                                             strf("P%zu_c = zs_span_f(L.p[%zu], S.p[%zu], zs_kv, v);", i, i, i)};
                 k.pro.push_back(strf("const bool P%zu_b = L.p[%zu].is_buffer != 0; const float P%zu_c = zs_const(L.p[%zu], v);", i, i, i, i));
                 v.kind = Val::buf; v.expr = strf("(P%zu_b ? x[%zu] : P%zu_c)", i, j, i);         // cob_to_buffer's switch (codegen_zig.zig:130-143)
                 v.cob_b = strf("P%zu_b", i); v.cob_c = strf("P%zu_c", i);
@@ -1174,6 +1194,8 @@ public:
                 break;
             case PK::one_of:
                 kind = "one_of";
+                k.pro_split[k.pro.size()] = {strf("uint32_t P%zu_tag = 0u; float P%zu_f = 0.0f;", i, i),
+                                             strf("P%zu_tag = zs_span_tag(L.p[%zu], S.p[%zu], zs_kv); P%zu_f = zs_span_payload(L.p[%zu], S.p[%zu], zs_kv);", i, i, i, i, i, i)};
                 k.pro.push_back(strf("const uint32_t P%zu_tag = L.p[%zu].u; const float P%zu_f = L.p[%zu].f;", i, i, i, i));
                 v.kind = Val::en; v.tag = strf("P%zu_tag", i);
                 v.payload = std::make_shared<Val>();
@@ -1636,6 +1658,76 @@ public:
         return out;
     }
 
+    // ================================================================ the per-voice sub-span form (script_rt.hip.h zs_span_walk)
+    // zs_paint_spans_<name>: the lane kernel's text, with the prologue of a paint (its params, NIC, the span's start and length,
+    // everything the top-level begin sink received) run per sub-span of the lane, and the epilogue's ends after it; the state stays
+    // in registers and is stored once.  Frame positions are relative to the lane's sub-span (delay chunks, tracks, curves).
+    Lines spans_kernel(const Kernel &k, size_t nin, size_t ni, int unroll) {
+        const std::string I = "    ", II = I + I;
+        auto rel = [](std::string l) {
+            const std::string from = "(i - L.start)", to = "(i - zs_s0)";
+            for (size_t at = l.find(from); at != std::string::npos; at = l.find(from, at + to.size())) l.replace(at, from.size(), to);
+            return l;
+        };
+        Lines out, once, begin, ends, frame;
+        for (size_t j = 0; j < k.pro.size(); j++) {
+            auto sp = k.pro_split.find(j);
+            if (sp != k.pro_split.end()) { once.push_back(sp->second.first); begin.push_back(sp->second.second); }
+            else if (k.pro_begin.count(j)) begin.push_back(rel(k.pro[j]));
+            else once.push_back(k.pro[j]);
+        }
+        for (const std::string &l : k.epi_ends) ends.push_back(rel(l));
+        for (const std::string &l : k.frame) frame.push_back(rel(resolve_sines(l, 0)));     // (exact only: no ZH_PAINT_TOLERANT form)
+        out.push_back(strf("extern \"C\" __global__ void __launch_bounds__(64) zs_paint_spans_%s(const ZsLaunch L, const ZsSpans S) {", k.name.c_str()));
+        out.push_back(I + "const uint32_t V = L.V;");
+        out.push_back(I + "const bool zs_live = blockIdx.x * 64 + threadIdx.x < V;");
+        out.push_back(I + "const uint32_t v = zs_live ? blockIdx.x * 64 + threadIdx.x : V - 1;   // (past the last voice: its loads, no sub-spans, no stores)");
+        out.push_back(I + "bool NIC = false;");
+        out.push_back(I + "uint32_t SPAN_LEN = 0u, zs_s0 = 0u;");
+        out.push_back(I + "(void)NIC; (void)SPAN_LEN; (void)zs_s0;");
+        std::string nulls, zeros;
+        for (size_t j = 0; j < ni; j++) { nulls += j ? ", nullptr" : "nullptr"; zeros += j ? ", 0" : "0"; }
+        out.push_back(I + strf("const float *ins[%zu] = {", ni) + nulls + "};");
+        out.push_back(I + strf("size_t istr[%zu] = {", ni) + zeros + "};");
+        out.push_back(I + strf("uint32_t ivo[%zu] = {", ni) + zeros + "};");
+        for (size_t j = 0; j < k.rows.size(); j++) out.push_back(I + strf("ins[%zu] = zs_row(L.p[%zu], v, istr[%zu], ivo[%zu]);", j, k.rows[j], j, j));
+        append(out, indent(once));
+        out.push_back(I + "bool zs_walk = false;");
+        out.push_back(I + "auto zs_begin = [&](const size_t zs_kv) ZH_INLINE_LAMBDA {");
+        out.push_back(II + "NIC = S.t.note_id_changed[zs_kv] != 0;");
+        out.push_back(II + "zs_s0 = S.t.start[zs_kv];");
+        out.push_back(II + "SPAN_LEN = S.t.end[zs_kv] - zs_s0;");
+        append(out, indent(indent(begin)));
+        out.push_back(I + "};");
+        out.push_back(I + "auto zs_end = [&]() ZH_INLINE_LAMBDA {");
+        append(out, indent(indent(ends)));
+        out.push_back(I + "};");
+        std::string all;
+        for (const std::string &t : k.quiet_terms) all += (all.empty() ? "" : " && ") + t;
+        out.push_back(I + strf("auto zs_body = [&](auto zs_q, uint32_t i, const float (&x)[%zu], float &o) ZH_INLINE_LAMBDA {", ni));
+        out.push_back(II + "constexpr bool ZS_Q = decltype(zs_q)::value; (void)ZS_Q;");
+        out.push_back(II + "(void)i; (void)x;");
+        if (!k.temps.empty()) {
+            std::string decl = "float ";
+            for (size_t j = 0; j < k.temps.size(); j++) decl += (j ? ", " : "") + k.temps[j] + " = 0.0f";
+            out.push_back(II + decl + ";");
+        }
+        append(out, indent(indent(frame)));
+        out.push_back(I + "};");
+        out.push_back(I + strf("auto zs_f = [&](uint32_t i, const float (&x)[%zu], float &o) ZH_INLINE_LAMBDA { zs_body(zs_tag<false>{}, i, x, o); };", ni));
+        if (all.empty()) {
+            out.push_back(I + strf("zs_span_walk<%d, %zu>(L, S, v, zs_live, ins, istr, ivo, zs_walk, zs_begin, zs_end, zs_f, [](int) { return false; }, zs_f);", unroll, nin));
+        } else {
+            out.push_back(I + "auto zs_quiet = [&](int zs_n) ZH_INLINE_LAMBDA -> bool { return " + all + "; };");
+            out.push_back(I + strf("auto zs_fq = [&](uint32_t i, const float (&x)[%zu], float &o) ZH_INLINE_LAMBDA { zs_body(zs_tag<true>{}, i, x, o); };", ni));
+            out.push_back(I + strf("zs_span_walk<%d, %zu>(L, S, v, zs_live, ins, istr, ivo, zs_walk, zs_begin, zs_end, zs_f, zs_quiet, zs_fq);", unroll, nin));
+        }
+        out.push_back(I + "if (!zs_live) return;");
+        append(out, indent(k.epi_stores));
+        out.push_back("}");
+        return out;
+    }
+
     std::string generate(const std::set<std::string> *only, std::vector<HipModuleMeta> &meta, int unroll_override, unsigned forms) {
         Lines out = {"// generated by zang_amd.zangscript (HIP backend) -- compile with zh_script_load / zh_script_compile",
                      "#include \"script_rt.hip.h\"", ""};
@@ -1785,6 +1877,7 @@ public:
             append(out, indent(k.epi_ends));
             append(out, indent(k.epi_stores));
             out.push_back("}");
+            if (forms & ZH_ZSCRIPT_FORM_SPANS) { out.push_back(""); append(out, spans_kernel(k, nin, ni, unroll)); }
             if (forms & (ZH_ZSCRIPT_FORM_ROLES | ZH_ZSCRIPT_FORM_ROLES_WORTH)) {
                 bool worth = false;
                 const Lines pc = role_kernel(k, nin, ni, preamble, (forms & 4u) ? 131072 : 65536, worth);    // (bit 2: an experiment, tools/r06_roles2.sh)

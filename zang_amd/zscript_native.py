@@ -41,6 +41,7 @@ def _package_bits(packages):
 
 FORM_ROLES = 1          # ZH_ZSCRIPT_FORM_ROLES: a role-wave kernel for every module that has more than one role
 FORM_ROLES_WORTH = 2    # ZH_ZSCRIPT_FORM_ROLES_WORTH: only where the emitter expects it to pay
+FORM_SPANS = 8          # ZH_ZSCRIPT_FORM_SPANS: zs_paint_spans_<name>, per-voice sub-spans in one launch (zh_script_module_paint_spans)
 
 
 class NativeScript:
