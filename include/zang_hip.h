@@ -699,15 +699,17 @@ ZH_API int zh_script_module_get_state(zh_script_module *m, uint32_t *host_words)
 ZH_API int zh_script_module_set_state(zh_script_module *m, const uint32_t *host_words);
 ZH_API int zh_script_module_paint(zh_script_module *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
                                   zh_bool note_id_changed, const zh_script_param *params, uint32_t n_params, uint32_t flags);
-/* Per-voice sub-spans of a generated module for one buffer: what NoteTracker -> PolyphonyDispatcher -> Trigger yields
- * (examples/example_script_runtime_poly.zig:146-164).  Device arrays [span_index][voice], like zh_span_table. */
+/* Per-voice sub-spans of a module for one buffer: what NoteTracker -> PolyphonyDispatcher -> Trigger yields
+ * (examples/example_script_runtime_poly.zig:146-164).  Device arrays [span_index][voice], like zh_span_table.  Taken by
+ * zh_script_module_paint_spans and by the builtin modules' zh_<module>_paint_spans (below), with zh_script_span_param. */
 typedef struct zh_script_span_table {
     uint32_t max_spans, reserved;
     const uint32_t *count;            /* [n_voices]                 */
     const uint32_t *start, *end;      /* [max_spans][n_voices]      */
     const uint8_t  *note_id_changed;  /* [max_spans][n_voices]      */
 } zh_script_span_table;
-/* Per-sub-span values of param i ([max_spans][n_voices] device arrays).  Both NULL: params[i] holds for every sub-span. */
+/* Per-sub-span values of param i ([max_spans][n_voices] device arrays).  Both NULL: params[i] holds for every sub-span.
+ * (zh_<module>_paint_spans: of span field i, ZH_<MODULE>_SPAN_*.) */
 typedef struct zh_script_span_param {
     const float    *f;   /* ZH_SP_CONSTANT, the constant of a ZH_SP_COB, the f32 payload of a ZH_SP_ENUM */
     const uint32_t *u;   /* ZH_SP_BOOLEAN (0/1), the index of a ZH_SP_ENUM */
@@ -727,6 +729,88 @@ typedef struct zh_script_span_param {
 ZH_API int zh_script_module_paint_spans(zh_script_module *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
                                         const zh_script_param *params, uint32_t n_params, const zh_script_span_param *span_params,
                                         const zh_script_span_table *table, uint32_t flags);
+
+/* ---------------------------------------------------------------- the builtin modules over per-voice sub-span tables
+ * A polyphonic voice paints its modules through Trigger: one paint(sub_span, outputs, temps, note_id_changed, params) per
+ * sub-span with that note's Params (src/zang/trigger.zig:80-105; examples/example_polyphony.zig:81-90,
+ * example_sampler.zig:96-105, example_song.zig:336-347).  zh_<module>_paint_spans does that for every voice of a module
+ * object in one launch, with the semantics of zh_script_module_paint_spans above: for each voice v and k < min(count[v],
+ * max_spans), paint(sub_span_k, ..., note_id_changed[k][v], params_k), each call's prologue and epilogue included, empty
+ * sub-spans too; a sub-span out of order ends the voice's list; frames no sub-span covers are left alone, ZH_PAINT_ZERO_FIRST
+ * writes all of [span_start, span_end).  span_params (NULL = none) is a host array [ZH_<MODULE>_SPAN_FIELDS]: entry i gives
+ * field i per sub-span (`f` float, `u` uint32 device arrays [max_spans][n_voices]).  A field without an array keeps its
+ * zh_<module>_paint meaning: a broadcast value, a per-voice array, or a cob buffer / input image read at the ABSOLUTE frame.
+ * The scalar sample_rate of the oscillators, Envelope and Decimator, the Sampler's sample and channel and the Noise seeds
+ * stay shared.  Tags in span arrays are not checked (out of range: unspecified output, no memory access outside the arguments).
+ * ZH_ERR_INVALID: NULL params, a NULL table array or max_spans == 0, `f` on a `u`-only field or `u` on an `f`-only field,
+ * a span array on a cob whose tag is ZH_COB_BUFFER, a tag out of range in params; ZH_ERR_UNSUPPORTED: ZH_PAINT_TOLERANT
+ * (the form is exact only).  ZH_PAINT_PARAMS_UNCHANGED is ignored: the form neither reads nor stores the constants it lets a
+ * PulseOsc / TriSawOsc paint reuse, and it counts as that module's previous paint -- the next flagged zh_<osc>_paint
+ * recomputes its constants.  No voices: ZH_OK, nothing runs.  No host sync: capturable; under ZH_CAPTURE_COALESCE it records what was held
+ * back first.  Module state follows the plain paints' bookkeeping, so span paints, plain paints and graph replays mix. */
+enum { ZH_SINEOSC_SPAN_FREQ = 0,          /* f (a constant freq only) */
+       ZH_SINEOSC_SPAN_PHASE,             /* f (a constant phase only) */
+       ZH_SINEOSC_SPAN_FIELDS };
+enum { ZH_PULSEOSC_SPAN_FREQ = 0,         /* f (a constant freq only) */
+       ZH_PULSEOSC_SPAN_COLOR,            /* f */
+       ZH_PULSEOSC_SPAN_FIELDS };
+enum { ZH_TRISAWOSC_SPAN_FREQ = 0,        /* f (a constant freq only) */
+       ZH_TRISAWOSC_SPAN_COLOR,           /* f */
+       ZH_TRISAWOSC_SPAN_FIELDS };
+enum { ZH_NOISE_SPAN_COLOR = 0,           /* u */
+       ZH_NOISE_SPAN_FIELDS };
+enum { ZH_ENVELOPE_SPAN_ATTACK = 0,       /* u = curve tag, f = duration */
+       ZH_ENVELOPE_SPAN_DECAY,            /* u = curve tag, f = duration */
+       ZH_ENVELOPE_SPAN_RELEASE,          /* u = curve tag, f = duration */
+       ZH_ENVELOPE_SPAN_SUSTAIN_VOLUME,   /* f */
+       ZH_ENVELOPE_SPAN_NOTE_ON,          /* u (0 / non-zero) */
+       ZH_ENVELOPE_SPAN_FIELDS };
+enum { ZH_GATE_SPAN_NOTE_ON = 0,          /* u (0 / non-zero) */
+       ZH_GATE_SPAN_FIELDS };
+enum { ZH_FILTER_SPAN_TYPE = 0,           /* u */
+       ZH_FILTER_SPAN_CUTOFF,             /* f (a constant cutoff only) */
+       ZH_FILTER_SPAN_RES,                /* f (a constant res only) */
+       ZH_FILTER_SPAN_FIELDS };
+enum { ZH_SAMPLER_SPAN_SAMPLE_RATE = 0,   /* f (negative: backwards, examples/example_sampler.zig:131-137) */
+       ZH_SAMPLER_SPAN_LOOP,              /* u (0 / non-zero) */
+       ZH_SAMPLER_SPAN_FIELDS };
+enum { ZH_DECIMATOR_SPAN_FAKE_SAMPLE_RATE = 0,   /* f */
+       ZH_DECIMATOR_SPAN_FIELDS };
+enum { ZH_DISTORTION_SPAN_TYPE = 0,       /* u */
+       ZH_DISTORTION_SPAN_INGAIN,         /* f */
+       ZH_DISTORTION_SPAN_OUTGAIN,        /* f */
+       ZH_DISTORTION_SPAN_OFFSET,         /* f */
+       ZH_DISTORTION_SPAN_FIELDS };
+ZH_API int zh_sineosc_paint_spans(zh_sineosc *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                  const zh_sineosc_params *params, const zh_script_span_param *span_params /*[ZH_SINEOSC_SPAN_FIELDS]*/,
+                                  const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_pulseosc_paint_spans(zh_pulseosc *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                   const zh_pulseosc_params *params, const zh_script_span_param *span_params /*[ZH_PULSEOSC_SPAN_FIELDS]*/,
+                                   const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_trisawosc_paint_spans(zh_trisawosc *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                    const zh_trisawosc_params *params, const zh_script_span_param *span_params /*[ZH_TRISAWOSC_SPAN_FIELDS]*/,
+                                    const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_noise_paint_spans(zh_noise *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                const zh_noise_params *params, const zh_script_span_param *span_params /*[ZH_NOISE_SPAN_FIELDS]*/,
+                                const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_envelope_paint_spans(zh_envelope *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                   const zh_envelope_params *params, const zh_script_span_param *span_params /*[ZH_ENVELOPE_SPAN_FIELDS]*/,
+                                   const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_gate_paint_spans(zh_gate *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                               const zh_gate_params *params, const zh_script_span_param *span_params /*[ZH_GATE_SPAN_FIELDS]*/,
+                               const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_filter_paint_spans(zh_filter *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                 const zh_filter_params *params, const zh_script_span_param *span_params /*[ZH_FILTER_SPAN_FIELDS]*/,
+                                 const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_sampler_paint_spans(zh_sampler *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                  const zh_sampler_params *params, const zh_script_span_param *span_params /*[ZH_SAMPLER_SPAN_FIELDS]*/,
+                                  const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_decimator_paint_spans(zh_decimator *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                    const zh_decimator_params *params, const zh_script_span_param *span_params /*[ZH_DECIMATOR_SPAN_FIELDS]*/,
+                                    const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_distortion_paint_spans(zh_distortion *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                     const zh_distortion_params *params, const zh_script_span_param *span_params /*[ZH_DISTORTION_SPAN_FIELDS]*/,
+                                     const zh_script_span_table *table, uint32_t flags);
 
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text

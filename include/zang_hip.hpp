@@ -159,7 +159,9 @@ namespace mod {
 
 // One class per module: `num_outputs`, `num_temps`, `Params` (the C ABI's params struct, fields in the Zig
 // declaration order) and paint(span, outputs, temps, note_id_changed, params) like the Zig declarations.
-#define ZANG_HIP_MODULE(Name, prefix, NT, CREATE_ARGS_DECL, CREATE_ARGS_USE)                                            \
+// SPANS: ZANG_HIP_SPANS(prefix) adds paint_spans(span, outputs, temps, params, span_params, table) -- zh_<prefix>_paint_spans: the
+// reference's Trigger loop (one paint per sub-span of a per-voice table) for every voice in one call
+#define ZANG_HIP_MODULE(Name, prefix, NT, CREATE_ARGS_DECL, CREATE_ARGS_USE, SPANS)                                     \
     class Name {                                                                                                          \
         zh_##prefix *h_ = nullptr;                                                                                        \
                                                                                                                           \
@@ -179,7 +181,15 @@ namespace mod {
             zang::check(zh_##prefix##_paint(h_, span.start, span.end, outputs.data(), NT ? temps.data() : nullptr,         \
                                             note_id_changed, &params, flags), "zh_" #prefix "_paint");                     \
         }                                                                                                                 \
+        SPANS                                                                                                             \
     };
+#define ZANG_HIP_SPANS(prefix)                                                                                            \
+    void paint_spans(zang::Span span, const std::array<zh_buf, 1> &outputs, const std::array<zh_buf, num_temps> &temps,   \
+                     const Params &params, const zh_script_span_param *span_params, const zh_script_span_table &table,  \
+                     uint32_t flags = ZH_PAINT_ADD) {                                                                     \
+        zang::check(zh_##prefix##_paint_spans(h_, span.start, span.end, outputs.data(), num_temps ? temps.data() : nullptr,  \
+                                              &params, span_params, &table, flags), "zh_" #prefix "_paint_spans");       \
+    }
 
 #define ZANG_HIP_NO_ARGS
 #define ZANG_HIP_COMMA_SEED , uint64_t first_seed = 0
@@ -187,22 +197,24 @@ namespace mod {
 #define ZANG_HIP_COMMA_F32 , zh_f32 init_value
 #define ZANG_HIP_USE_F32 , init_value
 
-ZANG_HIP_MODULE(SineOsc, sineosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)            // src/modules/SineOsc.zig
-ZANG_HIP_MODULE(PulseOsc, pulseosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)          // src/modules/PulseOsc.zig
-ZANG_HIP_MODULE(TriSawOsc, trisawosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)        // src/modules/TriSawOsc.zig
-ZANG_HIP_MODULE(Noise, noise, 0, ZANG_HIP_COMMA_SEED, ZANG_HIP_USE_SEED)            // src/modules/Noise.zig (seed = first_seed + voice)
-ZANG_HIP_MODULE(Envelope, envelope, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)          // src/modules/Envelope.zig
-ZANG_HIP_MODULE(Gate, gate, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)                  // src/modules/Gate.zig
-ZANG_HIP_MODULE(Filter, filter, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)              // src/modules/Filter.zig
-ZANG_HIP_MODULE(Decimator, decimator, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)        // src/modules/Decimator.zig
-ZANG_HIP_MODULE(Distortion, distortion, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)      // src/modules/Distortion.zig
-ZANG_HIP_MODULE(Cycle, cycle, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)                // src/modules/Cycle.zig
-ZANG_HIP_MODULE(Portamento, portamento, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)      // src/modules/Portamento.zig
+ZANG_HIP_MODULE(SineOsc, sineosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(sineosc))            // src/modules/SineOsc.zig
+ZANG_HIP_MODULE(PulseOsc, pulseosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(pulseosc))          // src/modules/PulseOsc.zig
+ZANG_HIP_MODULE(TriSawOsc, trisawosc, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(trisawosc))        // src/modules/TriSawOsc.zig
+ZANG_HIP_MODULE(Noise, noise, 0, ZANG_HIP_COMMA_SEED, ZANG_HIP_USE_SEED, ZANG_HIP_SPANS(noise))            // src/modules/Noise.zig (seed = first_seed + voice)
+ZANG_HIP_MODULE(Envelope, envelope, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(envelope))          // src/modules/Envelope.zig
+ZANG_HIP_MODULE(Gate, gate, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(gate))                  // src/modules/Gate.zig
+ZANG_HIP_MODULE(Filter, filter, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(filter))              // src/modules/Filter.zig
+ZANG_HIP_MODULE(Sampler, sampler, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(sampler))     // src/modules/Sampler.zig
+ZANG_HIP_MODULE(Decimator, decimator, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(decimator))        // src/modules/Decimator.zig
+ZANG_HIP_MODULE(Distortion, distortion, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_SPANS(distortion))      // src/modules/Distortion.zig
+ZANG_HIP_MODULE(Cycle, cycle, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)                // src/modules/Cycle.zig
+ZANG_HIP_MODULE(Portamento, portamento, 0, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS, ZANG_HIP_NO_ARGS)      // src/modules/Portamento.zig
 // the fused composites of examples/modules.zig (temps are accepted and unused: they live in registers)
-ZANG_HIP_MODULE(NiceInstrument, nice, 2, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32)      // :189-248, init(color)
-ZANG_HIP_MODULE(PMOscInstrument, pmosc, 3, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32)    // :80-128, init(release_duration)
+ZANG_HIP_MODULE(NiceInstrument, nice, 2, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32, ZANG_HIP_NO_ARGS)      // :189-248, init(color)
+ZANG_HIP_MODULE(PMOscInstrument, pmosc, 3, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32, ZANG_HIP_NO_ARGS)    // :80-128, init(release_duration)
 
 #undef ZANG_HIP_MODULE
+#undef ZANG_HIP_SPANS
 #undef ZANG_HIP_NO_ARGS
 #undef ZANG_HIP_COMMA_SEED
 #undef ZANG_HIP_USE_SEED

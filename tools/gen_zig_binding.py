@@ -54,6 +54,9 @@ HOST_MODULES = ["sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
 MANY_NAMES = {"outputs", "temps", "host", "filter", "impulses"}
 MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_dispatch", "out"),
                 ("zh_script_module_paint_spans", "params"), ("zh_script_module_paint_spans", "span_params"),
+                # zh_<module>_paint_spans reads ZH_<MODULE>_SPAN_FIELDS entries
+                *[("zh_%s_paint_spans" % m, "span_params") for m in ("sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
+                                                                     "filter", "sampler", "decimator", "distortion")],
                 # the batch call reads n_buffers elements of each
                 ("zh_nice_paint_mix_stereo_batch", "note_id_changed"), ("zh_nice_paint_mix_stereo_batch", "params")}
 # scalar pointer parameters that are a single out value, not an array

@@ -160,6 +160,19 @@ class ScriptSpanParam(C.Structure):        # zh_script_span_param
 
 ZSCRIPT_FORM_SPANS = 8
 
+# zh_<module>_paint_spans: the index of each span field in span_params (include/zang_hip.h ZH_<MODULE>_SPAN_*), in order
+SINEOSC_SPAN_FREQ, SINEOSC_SPAN_PHASE, SINEOSC_SPAN_FIELDS = range(3)
+PULSEOSC_SPAN_FREQ, PULSEOSC_SPAN_COLOR, PULSEOSC_SPAN_FIELDS = range(3)
+TRISAWOSC_SPAN_FREQ, TRISAWOSC_SPAN_COLOR, TRISAWOSC_SPAN_FIELDS = range(3)
+NOISE_SPAN_COLOR, NOISE_SPAN_FIELDS = range(2)
+(ENVELOPE_SPAN_ATTACK, ENVELOPE_SPAN_DECAY, ENVELOPE_SPAN_RELEASE, ENVELOPE_SPAN_SUSTAIN_VOLUME, ENVELOPE_SPAN_NOTE_ON,
+ ENVELOPE_SPAN_FIELDS) = range(6)
+GATE_SPAN_NOTE_ON, GATE_SPAN_FIELDS = range(2)
+FILTER_SPAN_TYPE, FILTER_SPAN_CUTOFF, FILTER_SPAN_RES, FILTER_SPAN_FIELDS = range(4)
+SAMPLER_SPAN_SAMPLE_RATE, SAMPLER_SPAN_LOOP, SAMPLER_SPAN_FIELDS = range(3)
+DECIMATOR_SPAN_FAKE_SAMPLE_RATE, DECIMATOR_SPAN_FIELDS = range(2)
+DISTORTION_SPAN_TYPE, DISTORTION_SPAN_INGAIN, DISTORTION_SPAN_OUTGAIN, DISTORTION_SPAN_OFFSET, DISTORTION_SPAN_FIELDS = range(5)
+
 
 class CurveNode(C.Structure):
     _fields_ = [("value", f32), ("t", f32)]
@@ -269,6 +282,7 @@ class DistortionHostParams(C.Structure):
 P = C.POINTER
 _hpaint = lambda params: [vp, vp, u32, u32, C.POINTER(C.POINTER(f32)), C.POINTER(C.POINTER(f32)), u32, C.POINTER(params)]
 _paint = lambda params: [vp, u32, u32, P(Buf), P(Buf), Bool, P(params), u32]
+_paint_spans = lambda params: [vp, u32, u32, P(Buf), P(Buf), P(params), P(ScriptSpanParam), P(ScriptSpanTable), u32]
 
 # name -> (restype, argtypes); must list every ZH_API symbol of include/zang_hip.h
 SIGNATURES = {
@@ -461,6 +475,16 @@ SIGNATURES = {
     "zh_mix_down": (C.c_int, [vp, vp, vp, u32, u32, u32, u32, f32]),
     "zh_nice_paint_spans": (C.c_int, [vp, u32, u32, P(Buf), P(Buf), f32, P(SpanTable), u32]),
     "zh_pmosc_paint_spans": (C.c_int, [vp, u32, u32, P(Buf), P(Buf), f32, P(SpanTable), u32]),
+    "zh_sineosc_paint_spans": (C.c_int, _paint_spans(SineOscParams)),
+    "zh_pulseosc_paint_spans": (C.c_int, _paint_spans(PulseOscParams)),
+    "zh_trisawosc_paint_spans": (C.c_int, _paint_spans(TriSawOscParams)),
+    "zh_noise_paint_spans": (C.c_int, _paint_spans(NoiseParams)),
+    "zh_envelope_paint_spans": (C.c_int, _paint_spans(EnvelopeParams)),
+    "zh_gate_paint_spans": (C.c_int, _paint_spans(GateParams)),
+    "zh_filter_paint_spans": (C.c_int, _paint_spans(FilterParams)),
+    "zh_sampler_paint_spans": (C.c_int, _paint_spans(SamplerParams)),
+    "zh_decimator_paint_spans": (C.c_int, _paint_spans(DecimatorParams)),
+    "zh_distortion_paint_spans": (C.c_int, _paint_spans(DistortionParams)),
     "zh_noise_state_init": (C.c_int, [vp, u64]),
     "zh_decimator_state_init": (C.c_int, [vp]),
     "zh_sineosc_paint_host": (C.c_int, _hpaint(SineOscHostParams)),

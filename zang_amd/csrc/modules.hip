@@ -14,6 +14,7 @@
 #include "seq.hip.h"
 #include "envelope.hip.h"
 #include "voices.hip.h"
+#include "span_walk.hip.h"
 #define ZH_FILTER_TP_PINK 1
 #include "filter_tp.hip.h"
 #include <vector>
@@ -934,67 +935,7 @@ struct zh_sampler : zh_flipper {
     float *t() const { return reinterpret_cast<float *>(cnt[cur]); }
 };
 
-struct SampleP {
-    const uint8_t *data;
-    uint64_t data_len;
-    uint32_t num_channels, sample_rate_in, format, channel, loop, whole;
-    int32_t num_samples;        // data.len / bytes_per_sample / num_channels (Sampler.zig:42)
-    double inv_num_samples;     // 1.0 / num_samples (0 when there are none): sampler_mod
-};
-
-// Sampler.zig:23-33.  FMT is a compile-time format (the kernel is instantiated per format and loop flag): with the
-// format switch, the loop test and the bounds test as branches inside the frame loop every frame was its own basic
-// block and paid the full latency of its PCM gathers; as straight-line code the loads of a chunk's 8 frames overlap.
-// `whole`: the PCM base is aligned to the sample size, so a sample is one load instead of byte_count byte gathers.
-template <int N> struct zint { static constexpr int value = N; };
-constexpr int kSampleEmpty = -1;                                     // no samples: every read is 0 (and nothing is loaded)
-template <int FMT>
-__device__ __forceinline__ float sampler_decode(const uint8_t *data, size_t i, bool whole) {
-    if constexpr (FMT == kSampleEmpty) return 0.0f;
-    else if constexpr (FMT == ZH_SAMPLE_U8) return ((float)data[i] - 127.5f) / 127.5f;
-    else {
-        constexpr int byte_count = FMT + 1;
-        const uint8_t *p = data + i * byte_count;
-        int32_t sval;
-        if constexpr (byte_count == 2) sval = whole ? (int16_t)*reinterpret_cast<const uint16_t *>(p) : (int16_t)((uint16_t)p[0] | ((uint16_t)p[1] << 8));
-        else if constexpr (byte_count == 3) {
-            const uint32_t u = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-            sval = (int32_t)(u << 8) >> 8;
-        } else sval = whole ? (int32_t)*reinterpret_cast<const uint32_t *>(p)
-                            : (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-        // `sval / max` with max = 2^(bits-1): dividing by a power of two and multiplying by its reciprocal are the
-        // same IEEE operation (both exact up to the one rounding of the result), so no divide sequence is needed
-        const float inv_max = 1.0f / (float)(1u << (byte_count * 8 - 1));
-        return (float)sval * inv_max;
-    }
-}
-
-// @mod(index, n) for n > 0 (floored, Sampler.zig:43): the quotient from one f64 multiply by 1/n (any i32 over any
-// positive i32 is far inside f64's 53 bits; the estimate is off by at most one), then two exact corrections -- a
-// dozen instructions instead of the ~40 of a 32-bit integer remainder.
-__device__ __forceinline__ int32_t sampler_mod(int32_t index, int32_t n, double inv_n) {
-    const int32_t q = (int32_t)floor((double)index * inv_n);
-    int32_t r = (int32_t)((uint32_t)index - (uint32_t)q * (uint32_t)n);
-    r = r < 0 ? r + n : r;
-    r = r >= n ? r - n : r;
-    return r;
-}
-
-// Sampler.zig:35-58 (num_samples == 0 with loop: division by zero in the reference; DEFINED as silence = kSampleEmpty)
-// the sample at an index that is already resolved (looped: inside [0, num_samples); else tested here)
-template <int FMT>
-__device__ __forceinline__ float sampler_at(const SampleP &s, int32_t index) {
-    if constexpr (FMT == kSampleEmpty) return 0.0f;
-    const bool in = index >= 0 && index < s.num_samples;
-    const size_t i = (size_t)(in ? index : 0) * s.num_channels + s.channel;
-    const float val = sampler_decode<FMT>(s.data, i, s.whole != 0);
-    return in ? val : 0.0f;
-}
-template <int FMT, bool LOOP>
-__device__ __forceinline__ float sampler_get_sample(const SampleP &s, int32_t index1) {
-    if constexpr (FMT == kSampleEmpty) return 0.0f;
-    return sampler_at<FMT>(s, LOOP ? sampler_mod(index1, s.num_samples, s.inv_num_samples) : index1);   // @mod: floored
-}
+// (SampleP and the sample reads live in voices.hip.h, next to SamplerLane)
 
 // One kernel, two launch shapes.  Sequential: grid.y = 1, ch = the whole span, t_in == t_out.  Few voices: grid.y frame
 // ranges of `ch` frames at once, one wave per (64 voices, range) -- the play position that reaches frame f0 is the start
@@ -1421,6 +1362,23 @@ template <class M> static int paint_check(M *m, uint32_t start, uint32_t end, co
     } while (0)
 
 static bool curve_ok(const zh_curve &c) { return c.tag <= ZH_CURVE_CUBED; }
+// the Sampler's shared sample as the kernels read it (channel < num_channels: the callers return before that)
+static int sampler_sample(const zh_sampler_params *p, SampleP &s) {
+    const uint64_t bps = (uint64_t)p->sample.format + 1;
+    s.data = p->sample.data;
+    s.data_len = p->sample.data_len;
+    s.num_channels = (uint32_t)p->sample.num_channels;
+    s.sample_rate_in = (uint32_t)p->sample.sample_rate;
+    s.format = p->sample.format;
+    s.channel = (uint32_t)p->channel;
+    s.loop = p->loop ? 1u : 0u;
+    s.whole = ((uintptr_t)p->sample.data % bps) == 0 ? 1u : 0u;
+    const uint64_t count = p->sample.data_len / bps / p->sample.num_channels;
+    if (count > 0x7fffffffull) return ZH_ERR_INVALID;                               // the reference's @intCast(i32, ...) traps (:42)
+    s.num_samples = (int32_t)count;
+    s.inv_num_samples = s.num_samples > 0 ? 1.0 / (double)s.num_samples : 0.0;
+    return ZH_OK;
+}
 static EnvParamsP mk_env_params(const zh_envelope_params *p) {
     return EnvParamsP{p->sample_rate, p->attack.tag, p->decay.tag, p->release.tag, mk_f32(p->attack.duration),
                       mk_f32(p->decay.duration), mk_f32(p->release.duration), mk_f32(p->sustain_volume), mk_bool(p->note_on)};
@@ -1997,20 +1955,9 @@ int zh_sampler_paint(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *
     if (p->channel >= p->sample.num_channels) {                                    // :87-89: nothing, not even the t reset
         return zf ? zh_zero(m->ctx, start, end, o) : ZH_OK;
     }
-    const uint64_t bps = (uint64_t)p->sample.format + 1;
     SampleP s;
-    s.data = p->sample.data;
-    s.data_len = p->sample.data_len;
-    s.num_channels = (uint32_t)p->sample.num_channels;
-    s.sample_rate_in = (uint32_t)p->sample.sample_rate;
-    s.format = p->sample.format;
-    s.channel = (uint32_t)p->channel;
-    s.loop = p->loop ? 1u : 0u;
-    s.whole = ((uintptr_t)p->sample.data % bps) == 0 ? 1u : 0u;
-    const uint64_t count = p->sample.data_len / bps / p->sample.num_channels;
-    if (count > 0x7fffffffull) return ZH_ERR_INVALID;                               // the reference's @intCast(i32, ...) traps (:42)
-    s.num_samples = (int32_t)count;
-    s.inv_num_samples = s.num_samples > 0 ? 1.0 / (double)s.num_samples : 0.0;
+    rc = sampler_sample(p, s);
+    if (rc) return rc;
     const Img img = mk_img(outputs[0]);
     const F32P rate = mk_f32(p->sample_rate);
     const BoolP nicp = mk_bool(note_id_changed);
@@ -2327,6 +2274,383 @@ int zh_distortion_paint(zh_distortion *m, uint32_t start, uint32_t end, const zh
     if (p->type == ZH_DISTORTION_OVERDRIVE) { if (zf) ZH_DIST(true, true); else ZH_DIST(false, true); }
     else { if (zf) ZH_DIST(true, false); else ZH_DIST(false, false); }
 #undef ZH_DIST
+    return zh_launch_status();
+}
+
+}  // extern "C"
+
+// =================================================================== span-table paints (zh_<module>_paint_spans)
+// For every voice, the reference's Trigger loop over its sub-spans in one launch (span_walk.hip.h module_spans): each adapter
+// below is a module's lane object with where its state lives and where each sub-span's values come from -- the span array
+// entry kv = k * V + v when the field has one, else the value the plain paint would use.  Tags from span arrays go into
+// compares and selects only (FilterLane / DistortionLane::begin, EnvLane's curves, the Noise colour), never an index.
+
+// ---- SineOsc: freq / phase per sub-span where they are constants; cob images read at the absolute frame
+struct SineSpanArgs { uint32_t V; const float *t_in; float *t_out; float sample_rate; CobP freq, phase; const float *sf, *sp; };
+template <bool FB, bool PB> struct SineSpans {
+    using Args = SineSpanArgs;
+    static constexpr int NIN = (FB ? 1 : 0) + (PB ? 1 : 0);
+    SineOscLane o;
+    float freq0, phase0, ph;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.t = a.t_in[v]; o.t_step = o.inv_sr = 0.0f;
+        freq0 = FB ? 0.0f : a.freq.c.get(v); phase0 = PB ? 0.0f : a.phase.c.get(v); ph = phase0;
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const {
+        if (FB) { in[0] = a.freq.b.p; istr[0] = a.freq.b.stride; }
+        if (PB) { in[FB ? 1 : 0] = a.phase.b.p; istr[FB ? 1 : 0] = a.phase.b.stride; }
+    }
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        o.begin(a.sample_rate, FB ? 0.0f : span_f(a.sf, kv, freq0));   // SineOsc.zig:44 / :66
+        ph = PB ? 0.0f : span_f(a.sp, kv, phase0);
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
+        val = o.template frame<FB>(FB ? x[0] : 0.0f, PB ? x[NI - 1] : ph);
+        return true;
+    }
+    __device__ __forceinline__ void end(const Args &) { o.end(); }  // :40
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.t_out[v] = o.t; }
+};
+ZH_MODULE_SPANS_KERNEL(k_sineosc_spans)
+
+// ---- Noise: the colour per sub-span; the taps restart from the module's `b` at every paint (Noise.zig:55, :68)
+struct NoiseSpanArgs { uint32_t V; uint64_t *s0, *s1, *s2, *s3; const float *b; uint32_t color; const uint32_t *sc; };
+struct NoiseSpans {
+    using Args = NoiseSpanArgs;
+    static constexpr int NIN = 0;
+    NoiseLane o;
+    float b0[7];
+    bool pink;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.r = ZXoshiro{a.s0[v], a.s1[v], a.s2[v], a.s3[v]};
+#pragma unroll
+        for (int j = 0; j < 7; j++) { b0[j] = a.b[(size_t)j * a.V + v]; o.b[j] = b0[j]; }
+        pink = false;
+    }
+    __device__ __forceinline__ void inputs(const Args &, const float **, size_t *) const {}
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        pink = span_u(a.sc, kv, a.color) == ZH_NOISE_PINK;
+#pragma unroll
+        for (int j = 0; j < 7; j++) o.b[j] = b0[j];                    // `var b = self.b` (:55)
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&)[NI], float &val) { val = o.frame_sel(pink); return true; }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const {
+        a.s0[v] = o.r.s0; a.s1[v] = o.r.s1; a.s2[v] = o.r.s2; a.s3[v] = o.r.s3;   // :71
+    }
+};
+ZH_MODULE_SPANS_KERNEL(k_noise_spans)
+
+// ---- Envelope: every curve's tag and duration, the sustain volume and note_on per sub-span (EnvLane: run-time tags)
+struct EnvSpanArgs {
+    uint32_t V; const uint32_t *in; uint32_t *out; EnvParamsP p;
+    const uint32_t *au, *du, *ru, *on; const float *af, *df, *rf, *sus;
+};
+struct EnvSpans {
+    using Args = EnvSpanArgs;
+    static constexpr int NIN = 0;
+    EnvLane e;
+    CurveP a0, d0, r0;
+    float sus0;
+    bool on0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        const size_t V = a.V;
+        e.state = a.in[v];
+        e.t = __builtin_bit_cast(float, a.in[V + v]); e.last_value = __builtin_bit_cast(float, a.in[2 * V + v]);
+        e.start = __builtin_bit_cast(float, a.in[3 * V + v]);
+        env_load(e, a.p, v);
+        a0 = e.attack; d0 = e.decay; r0 = e.release; sus0 = e.sustain_volume; on0 = e.note_on;
+        e.mode = ENV_MODE_NONE; e.cur_tag = 0; e.cur_step = e.cur_goal = e.cur_delta = 0.0f; e.m_painted = 0;
+    }
+    __device__ __forceinline__ void inputs(const Args &, const float **, size_t *) const {}
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool nic) {
+        e.attack = CurveP{span_u(a.au, kv, a0.tag), span_f(a.af, kv, a0.duration)};
+        e.decay = CurveP{span_u(a.du, kv, d0.tag), span_f(a.df, kv, d0.duration)};
+        e.release = CurveP{span_u(a.ru, kv, r0.tag), span_f(a.rf, kv, r0.duration)};
+        e.sustain_volume = span_f(a.sus, kv, sus0);
+        e.note_on = span_u(a.on, kv, on0 ? 1u : 0u) != 0;
+        e.begin(nic);                                                  // Envelope.zig:92-109's prologue
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&)[NI], float &val) { return e.frame(val); }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const {
+        const size_t V = a.V;
+        a.out[v] = e.state; a.out[V + v] = __builtin_bit_cast(uint32_t, e.t);
+        a.out[2 * V + v] = __builtin_bit_cast(uint32_t, e.last_value); a.out[3 * V + v] = __builtin_bit_cast(uint32_t, e.start);
+    }
+};
+ZH_MODULE_SPANS_KERNEL(k_envelope_spans)
+
+// ---- Gate (stateless): note_on per sub-span (Gate.zig:28-30: out += 1 while on)
+struct GateSpanArgs { uint32_t V; BoolP note_on; const uint32_t *on; };
+struct GateSpans {
+    using Args = GateSpanArgs;
+    static constexpr int NIN = 0;
+    bool on0, on;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) { on0 = a.note_on.get(v); on = false; }
+    __device__ __forceinline__ void inputs(const Args &, const float **, size_t *) const {}
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) { on = span_u(a.on, kv, on0 ? 1u : 0u) != 0; }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&)[NI], float &val) { val = 1.0f; return on; }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &, uint32_t) const {}
+};
+ZH_MODULE_SPANS_KERNEL(k_gate_spans)
+
+// ---- Filter: the type per sub-span (FilterLane::begin resolves it per lane), cutoff / res where they are constants
+struct FilterSpanArgs { uint32_t V; float *l, *b; CImg input; uint32_t type; CobP cutoff, res; const uint32_t *st; const float *sc, *sr; };
+template <bool CB, bool RB> struct FilterSpans {
+    using Args = FilterSpanArgs;
+    static constexpr int NIN = 1 + (CB ? 1 : 0) + (RB ? 1 : 0);
+    FilterLane o;
+    float c0, r0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.l = a.l[v]; o.b = a.b[v];
+        c0 = CB ? 0.0f : a.cutoff.c.get(v); r0 = RB ? 0.0f : a.res.c.get(v);
+        o.begin(ZH_FILTER_BYPASS, 0.0f, 0.0f);
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const {
+        in[0] = a.input.p; istr[0] = a.input.stride;
+        if (CB) { in[1] = a.cutoff.b.p; istr[1] = a.cutoff.b.stride; }
+        if (RB) { in[NIN - 1] = a.res.b.p; istr[NIN - 1] = a.res.b.stride; }
+    }
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        o.begin(span_u(a.st, kv, a.type), CB ? 0.0f : span_f(a.sc, kv, c0), RB ? 0.0f : span_f(a.sr, kv, r0));   // Filter.zig:90-118
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
+        val = o.template frame<CB, RB>(x[0], CB ? x[1] : 0.0f, RB ? x[NI - 1] : 0.0f);
+        return true;
+    }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.l[v] = o.l; a.b[v] = o.b; }
+};
+ZH_MODULE_SPANS_KERNEL(k_filter_spans)
+
+// ---- Sampler: the output rate (pitch; negative = backwards with loop) and the loop flag per sub-span (SamplerLane)
+struct SamplerSpanArgs { uint32_t V; const float *t_in; float *t_out; SampleP s; F32P rate; uint32_t loop; const float *sr; const uint32_t *sl; };
+template <int FMT> struct SamplerSpans {
+    using Args = SamplerSpanArgs;
+    static constexpr int NIN = 0;
+    SamplerLane o;
+    float rate0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.t = a.t_in[v]; rate0 = a.rate.get(v);
+        o.ratio = 0.0f; o.t0 = 0; o.n = 0; o.loop = false; o.silent = true; o.plain = false;
+    }
+    __device__ __forceinline__ void inputs(const Args &, const float **, size_t *) const {}
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool nic) {
+        o.begin(a.s, span_f(a.sr, kv, rate0), span_u(a.sl, kv, a.loop) != 0, nic);
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &a, const float (&)[NI], float &val) { return o.template frame<FMT>(a.s, val); }
+    __device__ __forceinline__ void end(const Args &a) { o.end(a.s); }
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.t_out[v] = o.t; }
+};
+ZH_MODULE_SPANS_KERNEL(k_sampler_spans)
+
+// ---- Decimator: the fake sample rate per sub-span (DecimatorLane::frame paints nothing in mode 2)
+struct DecSpanArgs { uint32_t V; const float *dval_in, *dcount_in; float *dval_out, *dcount_out; CImg input; float sample_rate; F32P fake; const float *sf; };
+struct DecSpans {
+    using Args = DecSpanArgs;
+    static constexpr int NIN = 1;
+    DecimatorLane o;
+    float fake0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.dval = a.dval_in[v]; o.dcount = a.dcount_in[v]; fake0 = a.fake.get(v);
+        o.mode = 2; o.ratio = 0.0f;
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const { in[0] = a.input.p; istr[0] = a.input.stride; }
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) { o.begin(a.sample_rate, span_f(a.sf, kv, fake0)); }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) { return o.frame(x[0], val); }
+    __device__ __forceinline__ void end(const Args &) { o.end(); }   // Decimator.zig:37-38
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.dval_out[v] = o.dval; a.dcount_out[v] = o.dcount; }
+};
+ZH_MODULE_SPANS_KERNEL(k_decimator_spans)
+
+// ---- Distortion (stateless): type, ingain, outgain and offset per sub-span
+struct DistSpanArgs { uint32_t V; CImg input; uint32_t type; F32P ingain, outgain, offset; const uint32_t *st; const float *si, *so, *sf; };
+struct DistSpans {
+    using Args = DistSpanArgs;
+    static constexpr int NIN = 1;
+    DistortionLane o;
+    float ig0, og0, of0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        ig0 = a.ingain.get(v); og0 = a.outgain.get(v); of0 = a.offset.get(v);
+        o.gain1 = o.offs = o.gain2 = 0.0f; o.overdrive = false;
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const { in[0] = a.input.p; istr[0] = a.input.stride; }
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        o.begin(span_u(a.st, kv, a.type), span_f(a.si, kv, ig0), span_f(a.so, kv, og0), span_f(a.sf, kv, of0));   // Distortion.zig:41-55
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) { val = o.frame(x[0]); return true; }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &, uint32_t) const {}
+};
+ZH_MODULE_SPANS_KERNEL(k_distortion_spans)
+
+// the checks every zh_<module>_paint_spans makes before its own (the span table, the kinds of the span arrays, the flags)
+#define ZH_SPANS_COMMON_CHECKS(NFIELDS, ...)                                                                               \
+    static const uint8_t kinds[NFIELDS] = {__VA_ARGS__};                                                                  \
+    (void)temps;                                                                                                          \
+    int rc = paint_check(m, start, end, outputs);                                                                         \
+    if (rc) return rc;                                                                                                    \
+    if (!p || !module_span_table_ok(table) || !module_span_params_ok(sp, kinds, NFIELDS)) return ZH_ERR_INVALID
+
+extern "C" {
+
+int zh_sineosc_paint_spans(zh_sineosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                           const zh_sineosc_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                           uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_SINEOSC_SPAN_FIELDS, SPAN_F, SPAN_F);
+    if (!cob_ok(p->freq, m->n, end) || !cob_ok(p->phase, m->n, end)) return ZH_ERR_INVALID;
+    const bool fb = p->freq.tag == ZH_COB_BUFFER, pb = p->phase.tag == ZH_COB_BUFFER;
+    if ((fb && span_has(sp, ZH_SINEOSC_SPAN_FREQ)) || (pb && span_has(sp, ZH_SINEOSC_SPAN_PHASE))) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const SineSpanArgs a{m->n, m->t(), reinterpret_cast<float *>(m->cnt[m->cur ^ 1]), p->sample_rate, mk_cob(p->freq), mk_cob(p->phase),
+                         span_fa(sp, ZH_SINEOSC_SPAN_FREQ), span_fa(sp, ZH_SINEOSC_SPAN_PHASE)};
+    if (fb && pb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<true, true>);
+    else if (fb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<true, false>);
+    else if (pb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<false, true>);
+    else ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<false, false>);
+    zh_flipper_painted(m);                  // read the current buffer, wrote the other (the frame-range paint's bookkeeping)
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_noise_paint_spans(zh_noise *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                         const zh_noise_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                         uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_NOISE_SPAN_FIELDS, SPAN_U);
+    if (p->color > ZH_NOISE_PINK) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const NoiseSpanArgs a{m->n, m->s[0], m->s[1], m->s[2], m->s[3], m->b, p->color, span_ua(sp, ZH_NOISE_SPAN_COLOR)};
+    ZH_MODULE_SPANS_LAUNCH(k_noise_spans, NoiseSpans);
+    return zh_launch_status();
+}
+
+int zh_envelope_paint_spans(zh_envelope *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                            const zh_envelope_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                            uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_ENVELOPE_SPAN_FIELDS, SPAN_F | SPAN_U, SPAN_F | SPAN_U, SPAN_F | SPAN_U, SPAN_F, SPAN_U);
+    if (!curve_ok(p->attack) || !curve_ok(p->decay) || !curve_ok(p->release)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const EnvSpanArgs a{m->n, m->cnt[m->cur], m->cnt[m->cur ^ 1], mk_env_params(p),
+                        span_ua(sp, ZH_ENVELOPE_SPAN_ATTACK), span_ua(sp, ZH_ENVELOPE_SPAN_DECAY), span_ua(sp, ZH_ENVELOPE_SPAN_RELEASE),
+                        span_ua(sp, ZH_ENVELOPE_SPAN_NOTE_ON), span_fa(sp, ZH_ENVELOPE_SPAN_ATTACK), span_fa(sp, ZH_ENVELOPE_SPAN_DECAY),
+                        span_fa(sp, ZH_ENVELOPE_SPAN_RELEASE), span_fa(sp, ZH_ENVELOPE_SPAN_SUSTAIN_VOLUME)};
+    ZH_MODULE_SPANS_LAUNCH(k_envelope_spans, EnvSpans);
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_gate_paint_spans(zh_gate *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                        const zh_gate_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                        uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_GATE_SPAN_FIELDS, SPAN_U);
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const GateSpanArgs a{m->n, mk_bool(p->note_on), span_ua(sp, ZH_GATE_SPAN_NOTE_ON)};
+    ZH_MODULE_SPANS_LAUNCH(k_gate_spans, GateSpans);
+    return zh_launch_status();
+}
+
+int zh_filter_paint_spans(zh_filter *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                          const zh_filter_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                          uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_FILTER_SPAN_FIELDS, SPAN_U, SPAN_F, SPAN_F);
+    if (p->type > ZH_FILTER_ALL_PASS || !buf_covers(p->input, m->n, end) || !cob_ok(p->cutoff, m->n, end) || !cob_ok(p->res, m->n, end))
+        return ZH_ERR_INVALID;
+    const bool cb = p->cutoff.tag == ZH_COB_BUFFER, rb = p->res.tag == ZH_COB_BUFFER;
+    if ((cb && span_has(sp, ZH_FILTER_SPAN_CUTOFF)) || (rb && span_has(sp, ZH_FILTER_SPAN_RES))) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const FilterSpanArgs a{m->n, m->l, m->b, mk_cimg(p->input), p->type, mk_cob(p->cutoff), mk_cob(p->res),
+                           span_ua(sp, ZH_FILTER_SPAN_TYPE), span_fa(sp, ZH_FILTER_SPAN_CUTOFF), span_fa(sp, ZH_FILTER_SPAN_RES)};
+    if (cb && rb) ZH_MODULE_SPANS_LAUNCH(k_filter_spans, FilterSpans<true, true>);
+    else if (cb) ZH_MODULE_SPANS_LAUNCH(k_filter_spans, FilterSpans<true, false>);
+    else if (rb) ZH_MODULE_SPANS_LAUNCH(k_filter_spans, FilterSpans<false, true>);
+    else ZH_MODULE_SPANS_LAUNCH(k_filter_spans, FilterSpans<false, false>);
+    return zh_launch_status();
+}
+
+int zh_sampler_paint_spans(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                           const zh_sampler_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                           uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_SAMPLER_SPAN_FIELDS, SPAN_F, SPAN_U);
+    if (p->sample.format > ZH_SAMPLE_S32_LSB || (p->sample.data_len && !p->sample.data)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    if (p->channel >= p->sample.num_channels) {                                    // :87-89: nothing, not even the t reset
+        zh_buf o = outputs[0];
+        o.voices = m->n;
+        return zf ? zh_zero(m->ctx, start, end, o) : ZH_OK;
+    }
+    SampleP s;
+    rc = sampler_sample(p, s);
+    if (rc) return rc;
+    hipStream_t st = m->ctx->stream;
+    const SamplerSpanArgs a{m->n, m->t(), reinterpret_cast<float *>(m->cnt[m->cur ^ 1]), s, mk_f32(p->sample_rate), p->loop ? 1u : 0u,
+                            span_fa(sp, ZH_SAMPLER_SPAN_SAMPLE_RATE), span_ua(sp, ZH_SAMPLER_SPAN_LOOP)};
+    switch (s.num_samples == 0 ? kSampleEmpty : (int)s.format) {
+    case kSampleEmpty: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<kSampleEmpty>); break;
+    case ZH_SAMPLE_U8: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_U8>); break;
+    case ZH_SAMPLE_S16_LSB: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_S16_LSB>); break;
+    case ZH_SAMPLE_S24_LSB: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_S24_LSB>); break;
+    default: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_S32_LSB>); break;
+    }
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_decimator_paint_spans(zh_decimator *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                             const zh_decimator_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                             uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_DECIMATOR_SPAN_FIELDS, SPAN_F);
+    if (!buf_covers(p->input, m->n, end)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const int c = m->cur;
+    const DecSpanArgs a{m->n, m->dval(c), m->dcount(c), m->dval(c ^ 1), m->dcount(c ^ 1), mk_cimg(p->input), p->sample_rate,
+                        mk_f32(p->fake_sample_rate), span_fa(sp, ZH_DECIMATOR_SPAN_FAKE_SAMPLE_RATE)};
+    ZH_MODULE_SPANS_LAUNCH(k_decimator_spans, DecSpans);
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_distortion_paint_spans(zh_distortion *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                              const zh_distortion_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                              uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_DISTORTION_SPAN_FIELDS, SPAN_U, SPAN_F, SPAN_F, SPAN_F);
+    if (p->type > ZH_DISTORTION_CLIP || !buf_covers(p->input, m->n, end)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const DistSpanArgs a{m->n, mk_cimg(p->input), p->type, mk_f32(p->ingain), mk_f32(p->outgain), mk_f32(p->offset),
+                         span_ua(sp, ZH_DISTORTION_SPAN_TYPE), span_fa(sp, ZH_DISTORTION_SPAN_INGAIN), span_fa(sp, ZH_DISTORTION_SPAN_OUTGAIN),
+                         span_fa(sp, ZH_DISTORTION_SPAN_OFFSET)};
+    ZH_MODULE_SPANS_LAUNCH(k_distortion_spans, DistSpans);
     return zh_launch_status();
 }
 

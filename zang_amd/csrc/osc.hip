@@ -16,6 +16,7 @@
 #include "dsp.hip.h"
 #include "seq.hip.h"
 #include "voices.hip.h"
+#include "span_walk.hip.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <vector>
@@ -797,6 +798,124 @@ int zh_trisawosc_paint(zh_trisawosc *m, uint32_t start, uint32_t end, const zh_b
 int zh_trisawosc_paint_batch(zh_trisawosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, uint32_t n_buffers,
                              const zh_trisawosc_params *p, uint32_t flags) { ZH_GUARD_EPOCH(m ? m->ctx : nullptr);
     return trisawosc_paint_n(m, start, end, outputs, n_buffers, p, flags);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ span-table paints (zh_<osc>_paint_spans; span_walk.hip.h)
+// One lane per voice walks its sub-spans: the constant-frequency path recomputes its per-voice constants at every sub-span's
+// begin (PulseOsc.zig:77-99) from that sub-span's freq and color and never reads or writes the constants table of
+// ZH_PAINT_PARAMS_UNCHANGED -- but the host forgets the table's params (tab.valid): the table is keyed by array POINTER, and a
+// flagged paint after this one may hold the same arrays with the contents this call was given, not those the table was built
+// from; that paint then recomputes (and stores) the constants.  The controlled-frequency path reads the image at the absolute frame.  The counters are read from
+// the current half of the double buffer and written to the other, and the module flips, as every constant-frequency paint does.
+struct OscSpanArgs { uint32_t V; const uint32_t *cnt_in; uint32_t *cnt_out; float *t; float sample_rate; CobP freq; F32P color; const float *sf, *sc; };
+template <bool FB> struct PulseSpans {
+    using Args = OscSpanArgs;
+    static constexpr int NIN = FB ? 1 : 0;
+    PulseOscLane o;
+    float freq0, color0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.cnt = a.cnt_in[v]; o.bad = true; o.k = PulseK{0, 0, 0.0f, 0.0f, 0.0f, 0.0f}; o.srf = o.sr8 = 0.0f;
+        freq0 = FB ? 0.0f : a.freq.c.get(v); color0 = a.color.get(v);
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const { if (FB) { in[0] = a.freq.b.p; istr[0] = a.freq.b.stride; } }
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        const float color = span_f(a.sc, kv, color0);
+        if (FB) o.begin_ctrl(a.sample_rate, color);                    // :123-132
+        else o.begin_const(a.sample_rate, span_f(a.sf, kv, freq0), color);   // :77-99
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
+        return FB ? o.frame_ctrl(x[0], val) : o.frame_const(val);
+    }
+    __device__ __forceinline__ void end(const Args &) {}
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.cnt_out[v] = o.cnt; }
+};
+ZH_MODULE_SPANS_KERNEL(k_pulseosc_spans)
+
+// TriSawOsc: the constant-frequency path's counter (double-buffered) and the controlled path's f32 phase (one buffer, updated
+// in place: each lane reads and writes its own voice's)
+template <bool FB> struct TriSawSpans {
+    using Args = OscSpanArgs;
+    static constexpr int NIN = FB ? 1 : 0;
+    TriSawOscLane o;
+    float freq0, color0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.cnt = a.cnt_in[v]; o.t = a.t[v];
+        o.bad = true; o.saw = false; o.all_saw = false; o.sample_rate = a.sample_rate;
+        o.k = TriSawK{0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        freq0 = FB ? 0.0f : a.freq.c.get(v); color0 = a.color.get(v);
+    }
+    __device__ __forceinline__ void inputs(const Args &a, const float **in, size_t *istr) const { if (FB) { in[0] = a.freq.b.p; istr[0] = a.freq.b.stride; } }
+    // (begin_const's all-saw vote counts the lanes that begin together: true only where each of them is a sawtooth, and a lane
+    // reads it only for itself)
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool) {
+        const float color = span_f(a.sc, kv, color0);
+        if (FB) o.begin_ctrl(a.sample_rate, color);                    // TriSawOsc.zig:120-150
+        else o.begin_const(a.sample_rate, span_f(a.sf, kv, freq0), color);   // :77-99
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
+        if (FB) { val = o.frame_ctrl(x[0]); return true; }
+        return o.frame_const(val);
+    }
+    __device__ __forceinline__ void end(const Args &) { if (FB) o.end_ctrl(); }   // :155
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.cnt_out[v] = o.cnt; a.t[v] = o.t; }
+};
+ZH_MODULE_SPANS_KERNEL(k_trisawosc_spans)
+
+template <class M, class P>
+static int osc_spans_check(M *m, uint32_t start, uint32_t end, const zh_buf *outputs, const P *p, const zh_script_span_param *sp,
+                           const zh_script_span_table *table, uint32_t flags, int freq_field, int nfields) {
+    static const uint8_t kinds[2] = {SPAN_F, SPAN_F};
+    if (!p) return ZH_ERR_INVALID;
+    int rc = osc_common_check(m, start, end, outputs, 1, p->sample_rate, p->freq);
+    if (rc) return rc;
+    if (!module_span_table_ok(table) || !module_span_params_ok(sp, kinds, nfields)) return ZH_ERR_INVALID;
+    if (p->freq.tag == ZH_COB_BUFFER && span_has(sp, freq_field)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    return ZH_OK;
+}
+
+extern "C" {
+
+int zh_pulseosc_paint_spans(zh_pulseosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                            const zh_pulseosc_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                            uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    (void)temps;
+    int rc = osc_spans_check(m, start, end, outputs, p, sp, table, flags, ZH_PULSEOSC_SPAN_FREQ, ZH_PULSEOSC_SPAN_FIELDS);
+    if (rc) return rc;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const OscSpanArgs a{m->n, m->cnt[m->cur], m->cnt[m->cur ^ 1], nullptr, p->sample_rate, mk_cob(p->freq), mk_f32(p->color),
+                        span_fa(sp, ZH_PULSEOSC_SPAN_FREQ), span_fa(sp, ZH_PULSEOSC_SPAN_COLOR)};
+    if (p->freq.tag == ZH_COB_BUFFER) ZH_MODULE_SPANS_LAUNCH(k_pulseosc_spans, PulseSpans<true>);
+    else ZH_MODULE_SPANS_LAUNCH(k_pulseosc_spans, PulseSpans<false>);
+    m->tab.valid = false;                   // this call is "the previous paint" of a later flagged one: its constants are not the table's
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_trisawosc_paint_spans(zh_trisawosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                             const zh_trisawosc_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                             uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    (void)temps;
+    int rc = osc_spans_check(m, start, end, outputs, p, sp, table, flags, ZH_TRISAWOSC_SPAN_FREQ, ZH_TRISAWOSC_SPAN_FIELDS);
+    if (rc) return rc;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    const OscSpanArgs a{m->n, m->cnt[m->cur], m->cnt[m->cur ^ 1], m->t, p->sample_rate, mk_cob(p->freq), mk_f32(p->color),
+                        span_fa(sp, ZH_TRISAWOSC_SPAN_FREQ), span_fa(sp, ZH_TRISAWOSC_SPAN_COLOR)};
+    if (p->freq.tag == ZH_COB_BUFFER) ZH_MODULE_SPANS_LAUNCH(k_trisawosc_spans, TriSawSpans<true>);
+    else ZH_MODULE_SPANS_LAUNCH(k_trisawosc_spans, TriSawSpans<false>);
+    m->tab.valid = false;                   // (as zh_pulseosc_paint_spans)
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
 }
 
 }  // extern "C"

@@ -194,6 +194,12 @@ struct NoiseLane {
         const float white = zrandom_float32(r) * 2.0f - 1.0f;         // :51 / :58
         return PINK ? pink_step(b, white) : white;                    // :59-66
     }
+    // the colour per lane (a span paint's voices may differ): ONE white draw per frame whatever the colour, then a select
+    __device__ __forceinline__ float frame_sel(bool pink) {
+        const float white = zrandom_float32(r) * 2.0f - 1.0f;
+        const float p = pink_step(b, white);                          // (the taps are restored at every begin(): a white lane's are never read)
+        return pink ? p : white;
+    }
 };
 
 // ---- Filter (src/modules/Filter.zig) -------------------------------------------------------------
@@ -288,6 +294,115 @@ struct DistortionLane {
         const float a0 = x * gain1 + offs;
         if (overdrive) return gain2 * zatanf(a0);                     // :50-51
         return gain2 * (a0 < -1.0f ? -1.0f : (a0 > 1.0f ? 1.0f : a0));   // :60-62
+    }
+};
+
+// ---- Sampler (src/modules/Sampler.zig) -----------------------------------------------------------
+struct SampleP {
+    const uint8_t *data;
+    uint64_t data_len;
+    uint32_t num_channels, sample_rate_in, format, channel, loop, whole;
+    int32_t num_samples;        // data.len / bytes_per_sample / num_channels (Sampler.zig:42)
+    double inv_num_samples;     // 1.0 / num_samples (0 when there are none): sampler_mod
+};
+
+// Sampler.zig:23-33.  FMT is a compile-time format (the kernels are instantiated per format): with the format switch, the
+// loop test and the bounds test as branches inside the frame loop every frame was its own basic block and paid the full
+// latency of its PCM gathers; as straight-line code the loads of a chunk's 8 frames overlap.
+// `whole`: the PCM base is aligned to the sample size, so a sample is one load instead of byte_count byte gathers.
+template <int N> struct zint { static constexpr int value = N; };
+constexpr int kSampleEmpty = -1;                                     // no samples: every read is 0 (and nothing is loaded)
+template <int FMT>
+__device__ __forceinline__ float sampler_decode(const uint8_t *data, size_t i, bool whole) {
+    if constexpr (FMT == kSampleEmpty) return 0.0f;
+    else if constexpr (FMT == ZH_SAMPLE_U8) return ((float)data[i] - 127.5f) / 127.5f;
+    else {
+        constexpr int byte_count = FMT + 1;
+        const uint8_t *p = data + i * byte_count;
+        int32_t sval;
+        if constexpr (byte_count == 2) sval = whole ? (int16_t)*reinterpret_cast<const uint16_t *>(p) : (int16_t)((uint16_t)p[0] | ((uint16_t)p[1] << 8));
+        else if constexpr (byte_count == 3) {
+            const uint32_t u = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+            sval = (int32_t)(u << 8) >> 8;
+        } else sval = whole ? (int32_t)*reinterpret_cast<const uint32_t *>(p)
+                            : (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+        // `sval / max` with max = 2^(bits-1): dividing by a power of two and multiplying by its reciprocal are the
+        // same IEEE operation (both exact up to the one rounding of the result), so no divide sequence is needed
+        const float inv_max = 1.0f / (float)(1u << (byte_count * 8 - 1));
+        return (float)sval * inv_max;
+    }
+}
+
+// @mod(index, n) for n > 0 (floored, Sampler.zig:43): the quotient from one f64 multiply by 1/n (any i32 over any
+// positive i32 is far inside f64's 53 bits; the estimate is off by at most one), then two exact corrections -- a
+// dozen instructions instead of the ~40 of a 32-bit integer remainder.
+__device__ __forceinline__ int32_t sampler_mod(int32_t index, int32_t n, double inv_n) {
+    const int32_t q = (int32_t)floor((double)index * inv_n);
+    int32_t r = (int32_t)((uint32_t)index - (uint32_t)q * (uint32_t)n);
+    r = r < 0 ? r + n : r;
+    r = r >= n ? r - n : r;
+    return r;
+}
+
+// Sampler.zig:35-58 (num_samples == 0 with loop: division by zero in the reference; DEFINED as silence = kSampleEmpty)
+// the sample at an index that is already resolved (looped: inside [0, num_samples); else tested here)
+template <int FMT>
+__device__ __forceinline__ float sampler_at(const SampleP &s, int32_t index) {
+    if constexpr (FMT == kSampleEmpty) return 0.0f;
+    const bool in = index >= 0 && index < s.num_samples;
+    const size_t i = (size_t)(in ? index : 0) * s.num_channels + s.channel;
+    const float val = sampler_decode<FMT>(s.data, i, s.whole != 0);
+    return in ? val : 0.0f;
+}
+template <int FMT, bool LOOP>
+__device__ __forceinline__ float sampler_get_sample(const SampleP &s, int32_t index1) {
+    if constexpr (FMT == kSampleEmpty) return 0.0f;
+    return sampler_at<FMT>(s, LOOP ? sampler_mod(index1, s.num_samples, s.inv_num_samples) : index1);   // @mod: floored
+}
+
+// One paint() call of Sampler.zig:77-136 for a voice whose rate and loop flag are its own (the sample and the channel are
+// shared; the host handles `channel >= num_channels`, :87-89, which touches nothing).  begin() = :91-105, frame() = one
+// sample of :105-114 (no resampling) or :116-130 (linear), end() = the play position's update after the loop (:114, :133-135).
+// Operations in the reference's order: the bits of k_sampler's general body.
+struct SamplerLane {
+    float t;                                                          // state (:69)
+    float ratio;
+    int32_t t0;                                                       // no resampling: the rounded start position
+    uint32_t n;                                                       // ... and frames painted so far
+    bool loop, silent, plain;
+    __device__ __forceinline__ void begin(const SampleP &s, float out_rate, bool loop_, bool note_id_changed) {
+        if (note_id_changed) t = 0.0f;                                // :91-93
+        loop = loop_;
+        ratio = (float)s.sample_rate_in / out_rate;                   // :97
+        silent = ratio < 0.0f && !loop;                               // :99-102: nothing more (t keeps the reset)
+        plain = ratio > 0.9999f && ratio < 1.0001f;                   // :105
+        t0 = zf32_to_i32(roundf(t));
+        n = 0;
+    }
+    template <int FMT> __device__ __forceinline__ float at(const SampleP &s, int32_t index1) const {
+        if constexpr (FMT == kSampleEmpty) return 0.0f;
+        else return sampler_at<FMT>(s, loop ? sampler_mod(index1, s.num_samples, s.inv_num_samples) : index1);
+    }
+    template <int FMT> __device__ __forceinline__ bool frame(const SampleP &s, float &val) {
+        if (silent) return false;
+        if (plain) {                                                  // :107-113
+            val = at<FMT>(s, (int32_t)((uint32_t)t0 + n));
+            n++;
+            return true;
+        }
+        const int32_t i0 = zf32_to_i32(floorf(t));                    // :117-128
+        const int32_t i1 = (int32_t)((uint32_t)i0 + 1u);
+        const float tfrac = (float)i1 - t;                            // :121
+        const float s0 = at<FMT>(s, i0);
+        const float s1 = at<FMT>(s, i1);
+        val = s0 * (1.0f - tfrac) + s1 * tfrac;
+        t += ratio;                                                   // :129
+        return true;
+    }
+    __device__ __forceinline__ void end(const SampleP &s) {
+        if (silent) return;
+        if (plain) t += (float)n;                                     // :114
+        if (t >= (float)s.data_len && loop) t -= (float)s.data_len;   // :133-135: data.len in BYTES (reference quirk, kept)
     }
 };
 

@@ -80,6 +80,41 @@ class _Module:
                 (abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD) | extra_flags)
         abi.check(rc, f"zh_{self._prefix}_paint")
 
+    # zh_<module>_paint_spans: the module's span fields in the C order (ZH_<MODULE>_SPAN_*), each (name, kind) with kind
+    # "constant" (an `f` array), "boolean" / "tag" (a `u` array) or "curve" (both: the tag in `u`, the duration in `f`)
+    _span_fields = ()
+
+    @classmethod
+    def span_spec(cls):
+        """the spec of a zang_amd.script.ScriptSpanTable for this module: [(field, kind, None)]"""
+        return [(n, k, None) for n, k in cls._span_fields]
+
+    @classmethod
+    def span_table(cls, count, start, end, note_id_changed, values=None):
+        """A per-voice sub-span table for paint_spans: count [V], start / end / note_id_changed [K][V] (host arrays), and
+        `values` {field: (f [K][V] or None, u [K][V] or None)} for the fields that vary per sub-span (span_spec())."""
+        from .script import ScriptSpanTable
+        return ScriptSpanTable(cls.span_spec(), count, start, end, note_id_changed, values)
+
+    def paint_spans(self, span, outputs, temps, params, table, zero_first=False):
+        """The reference's Trigger loop for every voice in one launch (zh_<module>_paint_spans): voice v runs paint(sub-span k,
+        ..., note_id_changed[k][v], params with the table's per-sub-span values) for each of its sub-spans in `table` (a
+        zang_amd.script.ScriptSpanTable, e.g. from span_table()).  `params`: the Params paint() takes, for every field the
+        table holds no array for.  Frames outside a voice's sub-spans are left alone, or zeroed with zero_first=True."""
+        rc = self._paint_spans(span, outputs, temps, params, table, abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, f"zh_{self._prefix}_paint_spans")
+
+    def _paint_spans(self, span, outputs, temps, params, table, flags, span_params=None):
+        """-> the return code; `span_params`: a ctypes ScriptSpanParam array to pass instead of the table's (the error tests)"""
+        cp = self._cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._span_fields])
+        if span_params is not None:
+            sp = span_params
+        fn = getattr(self.lib, f"zh_{self._prefix}_paint_spans")
+        rc = fn(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps), C.byref(cp), sp, C.byref(tb), flags)
+        self._keep = (cp, outputs, table)
+        return rc
+
     def _paint_batch(self, span, images, cparams, zero_first, extra_flags=0):
         outs = _bufarray(images)
         fn = getattr(self.lib, f"zh_{self._prefix}_paint_batch")
@@ -99,10 +134,15 @@ class SineOsc(_Module):
         freq: Any   # zang.constant(...) | zang.buffer(...)
         phase: Any
 
+    _span_fields = (("freq", "constant"), ("phase", "constant"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.SineOscParams(params.sample_rate, 0, params.freq, params.phase)
+
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, tolerant=False):
         """tolerant=True: ZH_PAINT_TOLERANT -- the sine in f32 (within 1e-5 of the peak, measured 3e-7); the phase state stays exact."""
-        cp = abi.SineOscParams(params.sample_rate, 0, params.freq, params.phase)
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first, abi.PAINT_TOLERANT if tolerant else 0)
 
 
 class PulseOsc(_Module):
@@ -119,8 +159,13 @@ class PulseOsc(_Module):
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, params_unchanged=False):
         """`params_unchanged`: the caller states that `params` (per-voice array contents included) are what the
         previous paint of this module got (ZH_PAINT_PARAMS_UNCHANGED, include/zang_hip.h); same bits either way."""
-        cp = abi.PulseOscParams(params.sample_rate, 0, params.freq, as_f32(params.color))
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_PARAMS_UNCHANGED if params_unchanged else 0)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first, abi.PAINT_PARAMS_UNCHANGED if params_unchanged else 0)
+
+    _span_fields = (("freq", "constant"), ("color", "constant"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.PulseOscParams(params.sample_rate, 0, params.freq, as_f32(params.color))
 
     def paint_batch(self, span, images, params, zero_first=False, params_unchanged=False):
         """len(images) consecutive paint calls with the same span and params, call b into images[b], as one launch
@@ -143,8 +188,13 @@ class TriSawOsc(_Module):
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, params_unchanged=False):
         """`params_unchanged`: the caller states that `params` (per-voice array contents included) are what the
         previous paint of this module got (ZH_PAINT_PARAMS_UNCHANGED, include/zang_hip.h); same bits either way."""
-        cp = abi.TriSawOscParams(params.sample_rate, 0, params.freq, as_f32(params.color))
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_PARAMS_UNCHANGED if params_unchanged else 0)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first, abi.PAINT_PARAMS_UNCHANGED if params_unchanged else 0)
+
+    _span_fields = (("freq", "constant"), ("color", "constant"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.TriSawOscParams(params.sample_rate, 0, params.freq, as_f32(params.color))
 
     def paint_batch(self, span, images, params, zero_first=False, params_unchanged=False):
         """len(images) consecutive paint calls with the same span and params, call b into images[b], as one launch
@@ -170,7 +220,13 @@ class Noise(_Module):
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, tolerant=False):
         """tolerant=True: ZH_PAINT_TOLERANT -- pink noise at few voices: the taps as chunks at once over exactly generated white
         noise (1e-5 of the voice's peak); white noise and the generator's state are always exact."""
-        self._paint(span, outputs, temps, note_id_changed, abi.NoiseParams(params.color), zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+
+    _span_fields = (("color", "tag"),)
+
+    @staticmethod
+    def _cparams(params):
+        return abi.NoiseParams(params.color)
 
 
 class Envelope(_Module):
@@ -187,10 +243,15 @@ class Envelope(_Module):
         sustain_volume: Any
         note_on: Any
 
+    _span_fields = (("attack", "curve"), ("decay", "curve"), ("release", "curve"), ("sustain_volume", "constant"), ("note_on", "boolean"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.EnvelopeParams(params.sample_rate, 0, params.attack, params.decay, params.release,
+                                  as_f32(params.sustain_volume), as_bool(params.note_on))
+
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
-        cp = abi.EnvelopeParams(params.sample_rate, 0, params.attack, params.decay, params.release,
-                                as_f32(params.sustain_volume), as_bool(params.note_on))
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
 
 
 class Gate(_Module):
@@ -201,8 +262,14 @@ class Gate(_Module):
     class Params:
         note_on: Any
 
+    _span_fields = (("note_on", "boolean"),)
+
+    @staticmethod
+    def _cparams(params):
+        return abi.GateParams(as_bool(params.note_on))
+
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
-        self._paint(span, outputs, temps, note_id_changed, abi.GateParams(as_bool(params.note_on)), zero_first)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
 
     def state(self):
         raise AttributeError("Gate has no state")
@@ -223,8 +290,13 @@ class Filter(_Module):
 
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, tolerant=False):
         """tolerant=True: ZH_PAINT_TOLERANT (opt-in, 1e-5 of the signal's peak instead of bits; include/zang_hip.h)."""
-        cp = abi.FilterParams(as_buf(params.input), params.type, 0, params.cutoff, params.res)
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+
+    _span_fields = (("type", "tag"), ("cutoff", "constant"), ("res", "constant"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.FilterParams(as_buf(params.input), params.type, 0, params.cutoff, params.res)
 
     @staticmethod
     def cutoffFromFrequency(frequency, sample_rate, ctx=None):
@@ -257,11 +329,16 @@ class Sampler(_Module):
         channel: int
         loop: bool
 
-    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+    _span_fields = (("sample_rate", "constant"), ("loop", "boolean"))
+
+    @staticmethod
+    def _cparams(params):
         s = params.sample
         cs = abi.Sample(s.num_channels, s.sample_rate, s.format, 0, s.data.data_ptr(), s.data.numel())
-        cp = abi.SamplerParams(as_f32(params.sample_rate), cs, params.channel, 1 if params.loop else 0, 0)
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first)
+        return abi.SamplerParams(as_f32(params.sample_rate), cs, params.channel, 1 if params.loop else 0, 0)
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
 
 
 class Decimator(_Module):
@@ -275,9 +352,14 @@ class Decimator(_Module):
         input: Any
         fake_sample_rate: Any
 
+    _span_fields = (("fake_sample_rate", "constant"),)
+
+    @staticmethod
+    def _cparams(params):
+        return abi.DecimatorParams(params.sample_rate, 0, as_buf(params.input), as_f32(params.fake_sample_rate))
+
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
-        cp = abi.DecimatorParams(params.sample_rate, 0, as_buf(params.input), as_f32(params.fake_sample_rate))
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
 
 
 class Distortion(_Module):
@@ -293,10 +375,15 @@ class Distortion(_Module):
         outgain: Any
         offset: Any
 
+    _span_fields = (("type", "tag"), ("ingain", "constant"), ("outgain", "constant"), ("offset", "constant"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.DistortionParams(as_buf(params.input), params.type, 0, as_f32(params.ingain),
+                                    as_f32(params.outgain), as_f32(params.offset))
+
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
-        cp = abi.DistortionParams(as_buf(params.input), params.type, 0, as_f32(params.ingain),
-                                  as_f32(params.outgain), as_f32(params.offset))
-        self._paint(span, outputs, temps, note_id_changed, cp, zero_first)
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
 
     def state(self):
         raise AttributeError("Distortion has no state")
