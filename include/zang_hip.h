@@ -904,6 +904,48 @@ ZH_API int zh_poly_voice_schedule(zh_poly_voice *pv, float sample_rate, const ui
                                   uint32_t max_spans, uint32_t *counts, uint32_t *start, uint32_t *end, void *params,
                                   uint8_t *note_id_changed);
 
+/* ---------------------------------------------------------------- voice bank: the same scheduling ON THE DEVICE
+ * N independent instruments, each the scheduling half of Voice(T) with the same polyphony, their songs and all scheduler
+ * state resident in device memory.  zh_voice_bank_schedule enqueues ONE kernel per 32 buffers on the context's stream that
+ * advances every instrument and writes the [span][voice] tables the *_paint_spans entry points read (voice = instrument *
+ * polyphony + slot): no host work per buffer beyond the launch, no sync, no copy.  Results equal zh_poly_voice_schedule's
+ * per instrument, bit for bit (a 33rd impulse dropped, an event behind the clock on frame 0, the tracker's f32 arithmetic).
+ * Songs are in CSR form: instrument i owns events [event_offsets[i], event_offsets[i + 1]) of paramses / t / note_ids
+ * (copied once; event_offsets[0] == 0, fewer than 2^32 - 1 events in all).  Records are params_size bytes, a multiple of 4,
+ * at most ZH_MAX_PARAMS_SIZE; note_on is the byte at note_on_offset.  The frames of one schedule call sum to less than 2^32.
+ * OVERFLOW: a voice's list stops at max_spans (count == max_spans), its Trigger state still advances as if every sub-span
+ * had been emitted, and a device counter is incremented per dropped sub-span: zh_voice_bank_overflows synchronises and
+ * returns it (33 rows per buffer always suffice).
+ * schedule never allocates: table capacity is 4 rows at creation, changed by zh_voice_bank_reserve (refused while a
+ * capture records: ZH_ERR_UNSUPPORTED); max_spans above it is ZH_ERR_INVALID.  Table addresses stay fixed between reserve
+ * calls, so a graph that holds schedule + paint can be replayed (`frames` is read when the call is made: a replay repeats
+ * the same buffer lengths); a reserve that changes the capacity INVALIDATES views and graphs made before it.  Capturable;
+ * under ZH_CAPTURE_COALESCE it records what was held back first.  Zero instruments: ZH_OK, nothing runs.
+ * Views are device pointers into the bank's tables, no copy: zh_voice_bank_span_param gives record word `word` as both `f`
+ * and `u` of one array (clear the one a field does not take); zh_voice_bank_span_table takes the word that holds freq. */
+typedef struct zh_voice_bank zh_voice_bank;
+typedef struct zh_voice_bank_instrument_state { uint64_t next_event; float t; uint32_t reserved; } zh_voice_bank_instrument_state;
+typedef struct zh_voice_bank_voice_state {
+    uint32_t used, note_on; uint64_t note_id, event_id;          /* the dispatcher's slot */
+    uint32_t has_note, reserved; uint64_t trigger_note_id;       /* the Trigger's carried note ... */
+    uint64_t trigger_event;                                      /* ... and the index of its event in the bank's arrays */
+} zh_voice_bank_voice_state;
+ZH_API int zh_voice_bank_create(zh_ctx *ctx, uint32_t n_instruments, uint32_t polyphony, uint32_t params_size, uint32_t note_on_offset,
+                                const uint64_t *event_offsets, const void *paramses, const float *t, const uint64_t *note_ids,
+                                zh_voice_bank **out);
+ZH_API int zh_voice_bank_destroy(zh_voice_bank *bank);
+ZH_API int zh_voice_bank_reset(zh_voice_bank *bank);                                                  /* example_song.zig:318-324 */
+ZH_API int zh_voice_bank_reserve(zh_voice_bank *bank, uint32_t max_rows);
+ZH_API int zh_voice_bank_schedule(zh_voice_bank *bank, float sample_rate, const uint32_t *frames, uint32_t n_buffers, uint32_t max_spans);
+ZH_API int zh_voice_bank_script_table(const zh_voice_bank *bank, uint32_t max_spans, zh_script_span_table *out);
+ZH_API int zh_voice_bank_span_param(const zh_voice_bank *bank, uint32_t word, zh_script_span_param *out);
+ZH_API int zh_voice_bank_span_table(const zh_voice_bank *bank, uint32_t max_spans, uint32_t freq_word, zh_span_table *out);
+ZH_API int zh_voice_bank_overflows(zh_voice_bank *bank, uint64_t *out);
+ZH_API int zh_voice_bank_get_state(zh_voice_bank *bank, zh_voice_bank_instrument_state *instruments /*[n]*/,
+                                   zh_voice_bank_voice_state *voices /*[n * polyphony]*/);
+ZH_API int zh_voice_bank_set_state(zh_voice_bank *bank, const zh_voice_bank_instrument_state *instruments,
+                                   const zh_voice_bank_voice_state *voices);
+
 /* ---------------------------------------------------------------- single-voice host-pointer wrappers
  * The literal one-voice form of a Zig module call: `state` is the Zig struct (in/out), `outputs[0]` and every
  * input buffer are HOST float[>= span_end] slices exactly like zang's []f32, params are plain values.  Each call

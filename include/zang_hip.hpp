@@ -153,6 +153,67 @@ inline void mixDown(Context &c, uint8_t *dst_dev, const float *mix_dev, uint32_t
     check(zh_mix_down(c.get(), dst_dev, mix_dev, n, audio_format, num_channels, channel_index, vol), "mixDown");
 }
 
+// A voice bank (zh_voice_bank_*): n instruments' NoteTracker -> PolyphonyDispatcher(polyphony) -> Triggers on the device
+// (examples/example_song.zig:287-350 without the paints).  schedule() enqueues the kernel that fills the span tables; the
+// views hand them to a module's paint_spans / zh_nice_paint_spans as device pointers.  Record = the song's NoteParamsType
+// (trivially copyable, sizeof a multiple of 4, at most 64 bytes); instrument i owns events [offsets[i], offsets[i + 1]).
+class VoiceBank {
+    zh_voice_bank *h_ = nullptr;
+    uint32_t n_, polyphony_;
+
+public:
+    template <class Record>
+    VoiceBank(Context &ctx, uint32_t polyphony, uint32_t note_on_offset, const std::vector<uint64_t> &offsets, const std::vector<Record> &records,
+              const std::vector<float> &t, const std::vector<uint64_t> &note_ids)
+        : n_(offsets.empty() ? 0u : (uint32_t)(offsets.size() - 1)), polyphony_(polyphony) {
+        if (records.size() != t.size() || note_ids.size() != t.size() || (n_ && offsets.back() != t.size()))
+            throw Error(ZH_ERR_INVALID, "VoiceBank: one record, one time and one note id per event");
+        check(zh_voice_bank_create(ctx.get(), n_, polyphony, (uint32_t)sizeof(Record), note_on_offset, n_ ? offsets.data() : nullptr, records.data(),
+                                   t.data(), note_ids.data(), &h_), "zh_voice_bank_create");
+    }
+    ~VoiceBank() { if (h_) zh_voice_bank_destroy(h_); }
+    VoiceBank(const VoiceBank &) = delete;
+    VoiceBank &operator=(const VoiceBank &) = delete;
+    zh_voice_bank *get() const { return h_; }
+    uint32_t instruments() const { return n_; }
+    uint32_t voices() const { return n_ * polyphony_; }
+    void reset() { check(zh_voice_bank_reset(h_), "zh_voice_bank_reset"); }
+    void reserve(uint32_t max_rows) { check(zh_voice_bank_reserve(h_, max_rows), "zh_voice_bank_reserve"); }   // invalidates views and graphs
+    void schedule(float sample_rate, const std::vector<uint32_t> &frames, uint32_t max_spans) {
+        check(zh_voice_bank_schedule(h_, sample_rate, frames.data(), (uint32_t)frames.size(), max_spans), "zh_voice_bank_schedule");
+    }
+    zh_script_span_table scriptTable(uint32_t max_spans) const {
+        zh_script_span_table t{};
+        check(zh_voice_bank_script_table(h_, max_spans, &t), "zh_voice_bank_script_table");
+        return t;
+    }
+    zh_script_span_param spanParamF(uint32_t word) const { zh_script_span_param p = spanParam(word); p.u = nullptr; return p; }
+    zh_script_span_param spanParamU(uint32_t word) const { zh_script_span_param p = spanParam(word); p.f = nullptr; return p; }
+    zh_span_table spanTable(uint32_t max_spans, uint32_t freq_word) const {
+        zh_span_table t{};
+        check(zh_voice_bank_span_table(h_, max_spans, freq_word, &t), "zh_voice_bank_span_table");
+        return t;
+    }
+    uint64_t overflows() { uint64_t n = 0; check(zh_voice_bank_overflows(h_, &n), "zh_voice_bank_overflows"); return n; }
+    struct State { std::vector<zh_voice_bank_instrument_state> instruments; std::vector<zh_voice_bank_voice_state> voices; };
+    State getState() {
+        State s{std::vector<zh_voice_bank_instrument_state>(n_), std::vector<zh_voice_bank_voice_state>(voices())};
+        check(zh_voice_bank_get_state(h_, s.instruments.data(), s.voices.data()), "zh_voice_bank_get_state");
+        return s;
+    }
+    void setState(const State &s) {
+        if (s.instruments.size() != n_ || s.voices.size() != voices()) throw Error(ZH_ERR_INVALID, "VoiceBank::setState: a state of another bank");
+        check(zh_voice_bank_set_state(h_, s.instruments.data(), s.voices.data()), "zh_voice_bank_set_state");
+    }
+
+private:
+    zh_script_span_param spanParam(uint32_t word) const {
+        zh_script_span_param p{};
+        check(zh_voice_bank_span_param(h_, word, &p), "zh_voice_bank_span_param");
+        return p;
+    }
+};
+
 }  // namespace zang
 
 namespace mod {
@@ -247,6 +308,16 @@ inline void paintBatch(PulseOsc &m, zang::Span span, const std::vector<zh_buf> &
 }
 inline void paintBatch(TriSawOsc &m, zang::Span span, const std::vector<zh_buf> &outputs, const TriSawOsc::Params &params, uint32_t flags = ZH_PAINT_ADD) {
     zang::check(zh_trisawosc_paint_batch(m.get(), span.start, span.end, outputs.data(), (uint32_t)outputs.size(), &params, flags), "zh_trisawosc_paint_batch");
+}
+
+// the fused composites over a per-voice sub-span table (zh_span_table: uploaded by the host, or a zang::VoiceBank's spanTable())
+inline void paintSpans(NiceInstrument &m, zang::Span span, const std::array<zh_buf, 1> &outputs, float sample_rate, const zh_span_table &table,
+                       uint32_t flags = ZH_PAINT_ADD) {
+    zang::check(zh_nice_paint_spans(m.get(), span.start, span.end, outputs.data(), nullptr, sample_rate, &table, flags), "zh_nice_paint_spans");
+}
+inline void paintSpans(PMOscInstrument &m, zang::Span span, const std::array<zh_buf, 1> &outputs, float sample_rate, const zh_span_table &table,
+                       uint32_t flags = ZH_PAINT_ADD) {
+    zang::check(zh_pmosc_paint_spans(m.get(), span.start, span.end, outputs.data(), nullptr, sample_rate, &table, flags), "zh_pmosc_paint_spans");
 }
 
 // mod.Filter.cutoffFromFrequency (Filter.zig:20-23), elementwise on the device

@@ -234,6 +234,15 @@ class PaintSpan(C.Structure):
     _fields_ = [("start", u64), ("end", u64), ("note_id_changed", u32), ("reserved", u32), ("params", C.c_uint8 * 64)]
 
 
+class VoiceBankInstrumentState(C.Structure):     # zh_voice_bank_instrument_state
+    _fields_ = [("next_event", u64), ("t", f32), ("reserved", u32)]
+
+
+class VoiceBankVoiceState(C.Structure):          # zh_voice_bank_voice_state
+    _fields_ = [("used", u32), ("note_on", u32), ("note_id", u64), ("event_id", u64), ("has_note", u32), ("reserved", u32),
+                ("trigger_note_id", u64), ("trigger_event", u64)]
+
+
 class HCob(C.Structure):
     _fields_ = [("tag", u32), ("constant", f32), ("buffer", C.POINTER(f32))]
 
@@ -417,6 +426,17 @@ SIGNATURES = {
     "zh_poly_voice_destroy": (C.c_int, [vp]),
     "zh_poly_voice_reset": (C.c_int, [vp]),
     "zh_poly_voice_schedule": (C.c_int, [vp, f32, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "zh_voice_bank_create": (C.c_int, [vp, u32, u32, u32, u32, vp, vp, vp, vp, P(vp)]),
+    "zh_voice_bank_destroy": (C.c_int, [vp]),
+    "zh_voice_bank_reset": (C.c_int, [vp]),
+    "zh_voice_bank_reserve": (C.c_int, [vp, u32]),
+    "zh_voice_bank_schedule": (C.c_int, [vp, f32, vp, u32, u32]),
+    "zh_voice_bank_script_table": (C.c_int, [vp, u32, P(ScriptSpanTable)]),
+    "zh_voice_bank_span_param": (C.c_int, [vp, u32, P(ScriptSpanParam)]),
+    "zh_voice_bank_span_table": (C.c_int, [vp, u32, u32, P(SpanTable)]),
+    "zh_voice_bank_overflows": (C.c_int, [vp, P(u64)]),
+    "zh_voice_bank_get_state": (C.c_int, [vp, P(VoiceBankInstrumentState), P(VoiceBankVoiceState)]),
+    "zh_voice_bank_set_state": (C.c_int, [vp, P(VoiceBankInstrumentState), P(VoiceBankVoiceState)]),
     "zh_zscript_compile": (C.c_int, [C.c_char_p, C.c_char_p, u32, P(vp), C.c_char_p, C.c_size_t]),
     "zh_zscript_destroy": (C.c_int, [vp]),
     "zh_zscript_free_text": (None, [vp]),

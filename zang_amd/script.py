@@ -398,7 +398,9 @@ class PolyScriptVoice:
     `note_params`: the module's params a note carries (constant / cob / boolean; `note_on` among them);
     `events`: [(t seconds, note id, {param: value})]."""
 
-    def __init__(self, module, polyphony, note_params, events):
+    def __init__(self, module, polyphony, note_params, events, device=False):
+        """device=True: the tables are filled on the device by a voice bank (zang_amd.bank) on the module's context and never
+        leave it -- the same bits, no host scheduling or upload per buffer; spans then start at frame 0."""
         assert module.n == polyphony
         self.module, self.polyphony = module, polyphony
         kinds = {n: k for n, k, _ in module.params}
@@ -420,6 +422,12 @@ class PolyScriptVoice:
         ids = np.array([e[1] for e in events], np.uint64)
         self._rec = rec
         self.lib = module.lib
+        self.bank = None
+        self.handle = None
+        if device:
+            from .bank import VoiceBank
+            self.bank = VoiceBank(module.program.ctx, polyphony, rec[:len(events)], [0, len(events)], t, ids, 4 * self.note_params.index("note_on"), rows=34)
+            return
         h = C.c_void_p()
         abi.check(self.lib.zh_poly_voice_create(polyphony, self.dtype.itemsize, 4 * self.note_params.index("note_on"), len(events),
                                                 rec.ctypes.data, t.ctypes.data, ids.ctypes.data, C.byref(h)), "zh_poly_voice_create")
@@ -429,6 +437,9 @@ class PolyScriptVoice:
         """the next buffer's sub-spans (frames [0, frames)) as a ScriptSpanTable"""
         P = self.polyphony
         cap = 34                                            # <= 32 impulses + carry-over per sub-voice and buffer
+        if self.bank is not None:
+            self.bank.schedule([frames], sample_rate, cap)
+            return self.bank.script_table(cap, {n: (j, "u" if k == "boolean" else "f") for j, (n, k) in enumerate(zip(self.note_params, self.kinds))})
         count = np.zeros(P, np.uint32)
         start = np.zeros((cap, P), np.uint32); end = np.zeros((cap, P), np.uint32)
         rec = np.zeros((cap, P), self.dtype); nic = np.zeros((cap, P), np.uint8)
@@ -443,6 +454,8 @@ class PolyScriptVoice:
 
     def paint(self, span, outputs, params, sample_rate):
         """one buffer: schedule it, then one paint_spans with zero_first (frames no note covers are zero).  Returns the table."""
+        if self.bank is not None and span.start:
+            raise ValueError("a device-scheduled voice paints spans that start at frame 0")
         table = self.schedule(span.end - span.start, sample_rate)
         if span.start:
             table.start += np.uint32(span.start); table.end += np.uint32(span.start)
@@ -450,6 +463,9 @@ class PolyScriptVoice:
         return table
 
     def close(self):
+        if self.bank is not None:
+            self.bank.close()
+            self.bank = None
         if self.handle:
             self.lib.zh_poly_voice_destroy(self.handle)
             self.handle = None

@@ -319,9 +319,14 @@ class NativeSongScheduler:
 class SongRenderer:
     """MainModule + write_wav's buffer loop on the GPU."""
 
-    def __init__(self, text, ctx, instruments=EXAMPLE_SONG_INSTRUMENTS, vol=0.25):
+    def __init__(self, text, ctx, instruments=EXAMPLE_SONG_INSTRUMENTS, vol=0.25, scheduler="host"):
+        """scheduler="device": the span tables are filled on the device, by one voice bank per instrument (zang_amd.bank) on that
+        instrument's stream, instead of by the host schedulers and an upload per buffer.  The same bits; opt-in."""
         import torch
         from . import modules as mod
+        if scheduler not in ("host", "device"):
+            raise ValueError("scheduler: 'host' or 'device'")
+        self.scheduler = scheduler
         self.ctx = ctx
         self.instruments = instruments
         self.notes = resolve_frequencies(compile_song(text, instruments), ctx)
@@ -351,10 +356,43 @@ class SongRenderer:
             self.views.append(self.image[:, col:col + inst.polyphony])
             col += inst.polyphony
         self.vol = vol
+        self.banks = []
+        if scheduler == "device":
+            from .bank import VoiceBank
+            for inst, ic, evs in zip(instruments, self.ictx, self.notes):
+                rec = np.zeros(len(evs), NativeSongScheduler._dtype)
+                # makeParams (example_song.zig:35-39 etc.): freq * freq_mul in f32, once per event instead of once per sub-span
+                rec["freq"] = np.array([e.freq for e in evs], np.float32) * np.float32(inst.freq_mul)
+                rec["note_on"] = [e.note_on for e in evs]
+                self.banks.append(VoiceBank(ic, inst.polyphony, rec, [0, len(evs)], [e.t for e in evs], [e.note_id for e in evs],
+                                            MyNoteParams.note_on.offset, rows=34))
+            self._bank_rows = 34
+
+    def _paint_from_banks(self, span, frame_counts, image):
+        """schedule + paint per instrument, each on its own stream; no table leaves the device"""
+        rows = 33 * len(frame_counts) + 1                      # <= 32 impulses + carry-over per buffer per sub-voice
+        if rows > self._bank_rows:
+            for b in self.banks:
+                b.reserve(rows)
+            self._bank_rows = rows
+        col = 0
+        for m, ic, inst, bank in zip(self.mods, self.ictx, self.instruments, self.banks):
+            view = image[:, col:col + inst.polyphony]
+            col += inst.polyphony
+            ic._stream.wait_stream(self.main_stream)
+            bank.schedule(frame_counts, float(AUDIO_SAMPLE_RATE), self._bank_rows)
+            m.paint_spans(span, [view], None, float(AUDIO_SAMPLE_RATE), bank.span_table(self._bank_rows, MyNoteParams.freq.offset // 4), zero_first=True)
+        for ic in self.ictx:
+            self.main_stream.wait_stream(ic._stream)
 
     def render_buffer(self, nframes=AUDIO_BUFFER_SIZE):
         """One write_wav iteration (write_wav.zig:58-93): returns nframes*2 bytes of s16 mono PCM."""
         span = zang.Span(0, nframes)
+        if self.banks:
+            self._paint_from_banks(span, [nframes], self.image)
+            zang.mixdownVoices(span, self.mix, self.image, zero_first=True, sequential=True, ctx=self.ctx)
+            zang.mixDown(self.pcm[:nframes * 2], self.mix[:nframes], zang.AudioFormat.signed16_lsb, 1, 0, self.vol, ctx=self.ctx)
+            return bytes(self.pcm[:nframes * 2].cpu().numpy())
         tables = self.sched.buffer(span)
         live = []                                                  # tables stay allocated until the main stream has joined
         for m, ic, view, per_voice in zip(self.mods, self.ictx, self.views, tables):
@@ -373,6 +411,8 @@ class SongRenderer:
         times per 1024-frame buffer), shifting buffer b's sub-spans by its start frame.  Trigger's carry-over
         already splits a note at every buffer boundary, so the per-call prologue/epilogue structure -- and
         the bits -- are unchanged, while the device walks len(frame_counts)*1024 frames per launch."""
+        if self.banks:
+            return int(sum(frame_counts)), list(frame_counts)
         return int(sum(frame_counts)), self.native.batch(frame_counts)
 
     def _launch_batch(self, prepared):
@@ -387,6 +427,9 @@ class SongRenderer:
         span = zang.Span(0, total)
         col = 0
         live = []
+        if self.banks:
+            self._paint_from_banks(span, per_inst, self._bimage)
+            per_inst = []
         for m, ic, inst, per_voice in zip(self.mods, self.ictx, self.instruments, per_inst):
             view = self._bimage[:, col:col + inst.polyphony]
             col += inst.polyphony
