@@ -195,6 +195,7 @@ def lib():
         "zo_math_powf": (f, [f, f]), "zo_math_expf": (f, [f]), "zo_math_logf": (f, [f]),
         "zo_math_sinf_n": (None, [_F, _F, z]), "zo_math_cosf_n": (None, [_F, _F, z]),
         "zo_math_atanf_n": (None, [_F, _F, z]), "zo_math_pow2f_n": (None, [_F, _F, z]),
+        "zo_math_powf_n": (None, [_F, _F, _F, z]), "zo_math_expf_n": (None, [_F, _F, z]), "zo_math_logf_n": (None, [_F, _F, z]),
         "zo_curve_init": (None, [C.POINTER(CurveModule)]),
         "zo_curve_paint": (None, [C.POINTER(CurveModule), z, z, _F, i32, f, u32, C.POINTER(CurveNode), z]),
         "zo_delay_init": (None, [C.POINTER(Delay), _F, z]),

@@ -685,6 +685,9 @@ void zo_math_sinf_n(const float *x, float *y, size_t n) { for (size_t i = 0; i <
 void zo_math_cosf_n(const float *x, float *y, size_t n) { for (size_t i = 0; i < n; i++) y[i] = zr_cosf(x[i]); }
 void zo_math_atanf_n(const float *x, float *y, size_t n) { for (size_t i = 0; i < n; i++) y[i] = zr_atanf(x[i]); }
 void zo_math_pow2f_n(const float *x, float *y, size_t n) { for (size_t i = 0; i < n; i++) y[i] = zr_powf(2.0f, x[i]); }
+void zo_math_powf_n(const float *x, const float *y, float *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = zr_powf(x[i], y[i]); }
+void zo_math_expf_n(const float *x, float *y, size_t n) { for (size_t i = 0; i < n; i++) y[i] = zr_expf(x[i]); }
+void zo_math_logf_n(const float *x, float *y, size_t n) { for (size_t i = 0; i < n; i++) y[i] = zr_logf(x[i]); }
 void zo_xoshiro_seq(uint64_t seed, uint64_t *state_out4, uint64_t *out, size_t n) {
     zr_xoshiro r; zr_xoshiro_init(&r, seed);
     memcpy(state_out4, r.s, 32);

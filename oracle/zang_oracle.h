@@ -118,4 +118,8 @@ double zo_bench_noise_filter(uint32_t voices, uint32_t frames, uint32_t buffers,
                              zo_noise *noise, zo_filter *flt, float *scratch);
 double zo_bench_nice(uint32_t voices, uint32_t frames, uint32_t buffers, float sample_rate, const float *freq,
                      zo_nice_instrument *inst, float *scratch);
+/* batch math probes of the tests (tests/test_gpu_pow.py compares tens of millions of values) */
+void zo_math_powf_n(const float *x, const float *y, float *out, size_t n);
+void zo_math_expf_n(const float *x, float *y, size_t n);
+void zo_math_logf_n(const float *x, float *y, size_t n);
 #endif

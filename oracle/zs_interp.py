@@ -188,7 +188,9 @@ class Instance:
                 n = len(a) if isinstance(a, np.ndarray) else len(b)
                 aa = a if isinstance(a, np.ndarray) else np.full(n, a, F32)
                 bb = b if isinstance(b, np.ndarray) else np.full(n, b, F32)
-                return np.array([self.L.zo_math_powf(float(x), float(y)) for x, y in zip(aa, bb)], F32)
+                aa, bb, out = np.ascontiguousarray(aa, F32), np.ascontiguousarray(bb, F32), np.empty(n, F32)
+                self.L.zo_math_powf_n(po.fptr(aa), po.fptr(bb), po.fptr(out), n)
+                return out
             return F32(self.L.zo_math_powf(float(a), float(b)))
         if op == "add":
             return a + b

@@ -537,6 +537,30 @@ def test_filter_known_answer_and_cutoff(ctx, oracle):
     util.assert_bitexact(got, ref, "cutoffFromFrequency")
 
 
+@pytest.mark.parametrize("sample_rate", [8000.0, 44100.0, 48000.0, 192000.0])
+def test_cutoff_from_frequency_edges(ctx, oracle, sample_rate):
+    """Filter.cutoffFromFrequency outside the audible band, bit for bit: negative, zero, above Nyquist (the clamp to 1), 1e9 and
+    beyond (zcosf's large-argument path), denormal, infinite and NaN frequencies (NaN where the oracle has NaN, nowhere else)"""
+    from zang_amd import modules as mod
+    rng = np.random.default_rng(int(sample_rate))
+    nyq = sample_rate / 2
+    f = np.concatenate([
+        rng.uniform(-30000.0, 0.0, 2048), rng.uniform(0.0, nyq, 2048), rng.uniform(nyq, 8 * nyq, 2048), nyq + np.arange(-8, 9) * 0.25,
+        rng.uniform(1.0, 2.0, 4096) * 2.0 ** rng.integers(29, 128, 4096) * rng.choice([-1.0, 1.0], 4096),      # 1e9 .. FLT_MAX
+        np.array([1e9, -1e9, 1e12, 3e38, -3e38, 0.0, -0.0, sample_rate, -sample_rate, sample_rate / 3, sample_rate / 6])]).astype(np.float32)
+    special = np.array([0x00000001, 0x80000001, 0x007fffff, 0x807fffff, 0x00800000, 0x7f7fffff, 0xff7fffff, 0x7f800000, 0xff800000,
+                        0x7fc00000, 0xffc00000, 0x7f800001], np.uint32).view(np.float32)
+    f = np.ascontiguousarray(np.concatenate([f, special, rng.integers(0, 1 << 32, 4096, dtype=np.uint64).astype(np.uint32).view(np.float32)]))
+    got = mod.Filter.cutoffFromFrequency(util.dev(f), sample_rate, ctx).cpu().numpy()
+    L = oracle.lib()
+    ref = np.array([L.zo_filter_cutoff_from_frequency(float(x), sample_rate) for x in f], np.float32)
+    nan = np.isnan(ref)
+    assert np.array_equal(np.isnan(got), nan)
+    bad = np.nonzero((got.view(np.uint32) != ref.view(np.uint32)) & ~nan)[0]
+    assert bad.size == 0, (sample_rate, bad.size, [(hex(int(f[i:i + 1].view(np.uint32)[0])), float(got[i]), float(ref[i])) for i in bad[:8]])
+    assert (ref == 1).sum() > 1000 and (ref == 0).sum() >= 2 and ((ref > 0) & (ref < 1)).sum() > 1000      # the clamp's three outcomes
+
+
 # ------------------------------------------------------------------ Sampler
 def _pcm(fmt, nframes, channels, seed):
     rng = np.random.default_rng(seed)
