@@ -321,6 +321,32 @@ enum { ZH_AUDIO_SIGNED8 = 0, ZH_AUDIO_SIGNED16_LSB = 1 };                       
 ZH_API int zh_mix_down(zh_ctx *ctx, uint8_t *dst, const float *mix, uint32_t n, uint32_t audio_format,
                        uint32_t num_channels, uint32_t channel_index, float vol);
 
+/* Grouped voice mixdown: the V voices of `src` are V / group_voices groups of P = group_voices consecutive voices (group g
+ * = voices [g*P, (g+1)*P): the sub-voices of instrument g of a voice bank), and every group is mixed on its own.  For each
+ * frame f of the span and each group g
+ *     s = start value;  s = s + src[f][g*P + 0];  s = s + src[f][g*P + 1];  ...  s = s + src[f][g*P + P-1]
+ * in f32, in that order -- the bits of P successive `+=` paints onto one buffer (basics.zig:31-36;
+ * example_song.zig:340-346), and of zh_mixdown_voices(ZH_MIX_SEQUENTIAL) on the group's column view -- in ONE launch for
+ * all groups, at the rate the image can be read.
+ *  - zh_mixdown_groups stores s to dst[g * dst_stride_floats + f].  The start value is +0 with ZH_PAINT_ZERO_FIRST,
+ *    otherwise what dst held (`+=`).
+ *  - zh_mixdown_groups_pcm passes s through zang.mixDown (mixdown.zig:28-86, exactly zh_mix_down's arithmetic and
+ *    rounding) and stores the 1 or 2 bytes at dst[g * dst_stride_bytes + (f * num_channels + channel_index) *
+ *    bytes_per_sample]; the other channels' bytes are not touched.  The start value is acc[g * acc_stride_floats + f], or
+ *    +0 when acc is NULL.  `acc` chains images: voices of several kinds live in several images, so mix the first into
+ *    an f32 row per group, the next ones `+=` onto it, and the last through this call with acc = those rows -- the bits
+ *    of one sequential sum over all the sub-voices followed by zh_mix_down.
+ * Frames outside the span are neither read nor written.  ZH_ERR_INVALID: a NULL ctx, dst or image; group_voices == 0 or not
+ * a divisor of src.voices; span_end < span_start or > src.frames; with more than one group, a stride that does not hold
+ * span_end samples; an unknown audio_format, num_channels == 0, channel_index >= num_channels.  ZH_ERR_UNSUPPORTED:
+ * ZH_PAINT_TOLERANT.  No groups or an empty span: ZH_OK, nothing is launched.  Neither call synchronises or allocates: both
+ * may be recorded into a graph. */
+ZH_API int zh_mixdown_groups(zh_ctx *ctx, uint32_t span_start, uint32_t span_end, float *dst, size_t dst_stride_floats,
+                             zh_buf src, uint32_t group_voices, uint32_t flags);
+ZH_API int zh_mixdown_groups_pcm(zh_ctx *ctx, uint32_t span_start, uint32_t span_end, uint8_t *dst, size_t dst_stride_bytes,
+                                 zh_buf src, uint32_t group_voices, const float *acc /* NULL: start from 0 */, size_t acc_stride_floats,
+                                 uint32_t audio_format, uint32_t num_channels, uint32_t channel_index, float vol);
+
 /* ---------------------------------------------------------------- SineOsc (src/modules/SineOsc.zig) */
 typedef struct zh_sineosc zh_sineosc;
 typedef struct zh_sineosc_params { float sample_rate; uint32_t reserved; zh_cob freq; zh_cob phase; } zh_sineosc_params; /* :10-14 */

@@ -152,6 +152,19 @@ inline void mixDown(Context &c, uint8_t *dst_dev, const float *mix_dev, uint32_t
                     uint32_t channel_index, float vol) {
     check(zh_mix_down(c.get(), dst_dev, mix_dev, n, audio_format, num_channels, channel_index, vol), "mixDown");
 }
+// every group of `group_voices` consecutive voices of an image on its own, added in voice order (the bits of successive `+=`
+// paints): dst_dev[g * dst_stride_floats + f] (+)= src[f][g*P] + ... + src[f][g*P + P-1], all groups in one launch
+inline void mixdownGroups(Context &c, Span s, float *dst_dev, size_t dst_stride_floats, zh_buf src, uint32_t group_voices,
+                          uint32_t flags = ZH_PAINT_ADD) {
+    check(zh_mixdown_groups(c.get(), s.start, s.end, dst_dev, dst_stride_floats, src, group_voices, flags), "mixdownGroups");
+}
+// the same sums (starting from acc_dev's rows, or from 0 when it is null) straight through zang.mixDown into one PCM row per group
+inline void mixdownGroupsPcm(Context &c, Span s, uint8_t *dst_dev, size_t dst_stride_bytes, zh_buf src, uint32_t group_voices,
+                             const float *acc_dev, size_t acc_stride_floats, uint32_t audio_format, uint32_t num_channels,
+                             uint32_t channel_index, float vol) {
+    check(zh_mixdown_groups_pcm(c.get(), s.start, s.end, dst_dev, dst_stride_bytes, src, group_voices, acc_dev, acc_stride_floats, audio_format,
+                                num_channels, channel_index, vol), "mixdownGroupsPcm");
+}
 
 // A voice bank (zh_voice_bank_*): n instruments' NoteTracker -> PolyphonyDispatcher(polyphony) -> Triggers on the device
 // (examples/example_song.zig:287-350 without the paints).  schedule() enqueues the kernel that fills the span tables; the

@@ -338,6 +338,8 @@ SIGNATURES = {
     "zh_multiply_scalar": (C.c_int, [vp, u32, u32, Buf, Buf, F32]),
     "zh_multiply_with_scalar": (C.c_int, [vp, u32, u32, Buf, F32]),
     "zh_mixdown_voices": (C.c_int, [vp, u32, u32, vp, Buf, u32]),
+    "zh_mixdown_groups": (C.c_int, [vp, u32, u32, vp, C.c_size_t, Buf, u32, u32]),
+    "zh_mixdown_groups_pcm": (C.c_int, [vp, u32, u32, vp, C.c_size_t, Buf, u32, vp, C.c_size_t, u32, u32, u32, f32]),
     "zh_ipc_alloc": (C.c_int, [vp, C.c_size_t, P(vp), vp]),
     "zh_ipc_open": (C.c_int, [vp, vp, P(vp)]),
     "zh_ipc_close": (C.c_int, [vp, vp]),

@@ -4,6 +4,8 @@ argument order as the reference, acting on [frame][voice] device images of many 
 """
 from dataclasses import dataclass
 
+import torch
+
 from . import abi
 from .runtime import as_buf, as_bool, as_f32, default_context
 
@@ -129,6 +131,29 @@ def mixDown(dst, mix_buffer, audio_format, num_channels, channel_index, vol, ctx
     assert dst.numel() == n * bps * num_channels            # mixdown.zig:35,66
     abi.check(c.lib.zh_mix_down(c.handle, dst.data_ptr(), mix_buffer.data_ptr(), n, audio_format, num_channels,
                                 channel_index, float(vol)), "zh_mix_down")
+
+
+def mixdownGroups(span, dst, src, group_voices, zero_first=False, ctx=None):
+    """Every group of `group_voices` consecutive voices of `src` mixed on its own, in voice order in f32 (the bits of successive
+    `+=` paints): dst[g][f] (+)= src[f][g*P] + ... + src[f][g*P + P-1].  dst: float32 CUDA tensor [groups, >= span.end]."""
+    c = _ctx(ctx)
+    b = as_buf(src)
+    assert dst.dtype == torch.float32 and dst.dim() == 2 and dst.stride(1) == 1 and dst.shape[0] * group_voices == b.voices
+    flags = abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD
+    abi.check(c.lib.zh_mixdown_groups(c.handle, span.start, span.end, dst.data_ptr(), dst.stride(0), b, group_voices, flags), "zh_mixdown_groups")
+
+
+def mixdownGroupsPcm(span, dst, src, group_voices, audio_format, num_channels, channel_index, vol, acc=None, ctx=None):
+    """The same per-group sums -- started from acc[g][f] (float32 [groups, >= span.end]) when given, so that images of several
+    kinds chain in the reference's order -- through zang.mixDown into dst[g] (uint8 CUDA tensor [groups, >= span.end *
+    num_channels * bytes_per_sample]); the other channels' bytes stay."""
+    c = _ctx(ctx)
+    b = as_buf(src)
+    assert dst.dtype == torch.uint8 and dst.dim() == 2 and dst.stride(1) == 1 and dst.shape[0] * group_voices == b.voices
+    assert acc is None or (acc.dtype == torch.float32 and acc.dim() == 2 and acc.stride(1) == 1 and acc.shape[0] == dst.shape[0])
+    abi.check(c.lib.zh_mixdown_groups_pcm(c.handle, span.start, span.end, dst.data_ptr(), dst.stride(0), b, group_voices,
+                                          acc.data_ptr() if acc is not None else None, acc.stride(0) if acc is not None else 0,
+                                          audio_format, num_channels, channel_index, float(vol)), "zh_mixdown_groups_pcm")
 
 
 # ---- event scheduling (src/zang/notes.zig, src/zang/trigger.zig): re-exported like src/zang.zig does
