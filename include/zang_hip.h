@@ -15,7 +15,11 @@
  *
  * Like the reference, every paint ACCUMULATES into outputs[0] (`+=`), and the caller
  * zeroes first (e.g. examples/modules.zig:220-221).  ZH_PAINT_ZERO_FIRST fuses that
- * `zang.zero(span, out)` into the paint kernel (bit-identical to zero-then-paint).
+ * `zang.zero(span, out)` into the paint kernel (bit-identical to zero-then-paint).  A paint
+ * whose input or control image overlaps outputs[0] reads the zeros, as zero-then-paint does:
+ * the library then zeroes the span first and paints with ZH_PAINT_ADD.  An image that IS
+ * outputs[0] (same pointer and stride) is read in the reference's order: SineOsc, TriSawOsc and
+ * Cycle read a frame's control value after they have added to that frame, every other module before.
  *
  * All entry points return 0 on success, a hipError_t (> 0) when HIP failed, or a negative
  * ZH_ERR_* for bad arguments.  Work is enqueued on the context's stream and is

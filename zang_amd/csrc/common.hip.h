@@ -247,6 +247,16 @@ static inline bool bufs_alias(const zh_buf &a, const zh_buf &b) {
     return a.ptr < be && b.ptr < ae;
 }
 static inline bool cob_aliases(const zh_cob &c, const zh_buf &b) { return c.tag == ZH_COB_BUFFER && bufs_alias(c.buffer, b); }
+// ZH_PAINT_ZERO_FIRST is "zang.zero(span, out), then the paint": a paint that READS an image overlapping outputs[0] must read the
+// zeros.  The fused forms start the output from 0 without storing it first, so they would read the image's old contents: every entry
+// point that reads an image calls this with whether one overlaps the output -- the span is zeroed now and the paint goes on as an ADD.
+static inline int zh_zero_first_aliased(zh_ctx *ctx, uint32_t start, uint32_t end, const zh_buf &out, uint32_t n_voices, bool aliased, uint32_t &flags) {
+    if (!aliased || !(flags & ZH_PAINT_ZERO_FIRST)) return ZH_OK;
+    flags &= ~(uint32_t)ZH_PAINT_ZERO_FIRST;
+    zh_buf o = out;
+    o.voices = n_voices;
+    return end > start ? zh_zero(ctx, start, end, o) : ZH_OK;
+}
 static inline bool cob_ok(const zh_cob &c, uint32_t n_voices, uint32_t span_end) {
     if (c.tag == ZH_COB_CONSTANT) return true;
     if (c.tag == ZH_COB_BUFFER) return buf_covers(c.buffer, n_voices, span_end);

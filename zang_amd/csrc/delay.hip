@@ -596,6 +596,7 @@ int zh_delay_paint(zh_delay *m, uint32_t start, uint32_t end, const zh_buf *outp
     (void)temps; (void)note_id_changed;                                            // examples/modules.zig:370-371
     if (!m || !outputs || !p || end < start || !buf_covers(outputs[0], m->d.n, end) || !buf_covers(p->input, m->d.n, end)) return ZH_ERR_INVALID;
     if (m->d.n == 0 || end == start) return ZH_OK;
+    if (int rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->d.n, bufs_alias(p->input, outputs[0]), flags)) return rc;
     const bool chunked = delay_can_chunk(m->d, outputs[0], p->input);
     // delay 300, 1,024 frames, walk -> independent frames (three launches): 57 -> 13 us at 4,096 voices, 75 -> 31 at 16,384,
     // 423 -> 271 at 131,072: at every voice count
@@ -668,6 +669,7 @@ int zh_filtered_echoes_paint(zh_filtered_echoes *m, uint32_t start, uint32_t end
     (void)temps; (void)note_id_changed;
     if (!m || !outputs || !p || end < start || !buf_covers(outputs[0], m->d.n, end) || !buf_covers(p->input, m->d.n, end)) return ZH_ERR_INVALID;
     if (m->d.n == 0 || end == start) return ZH_OK;
+    if (int rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->d.n, bufs_alias(p->input, outputs[0]), flags)) return rc;
     const bool chunked = delay_can_chunk(m->d, outputs[0], p->input);
     // ZH_PAINT_TOLERANT, few voices: pieces of <= delay_samples frames, each a time-parallel Filter paint (k_fe_tp_a / _b above).
     // Not for a span of more than three pieces (a delay much shorter than the span): a launch pair per piece, ~10 us each at

@@ -35,7 +35,7 @@ struct zh_sineosc : zh_flipper {
     float *t() const { return reinterpret_cast<float *>(cnt[cur]); }
 };
 
-template <bool ZF, bool FB, bool PB, bool TOL = false>
+template <bool ZF, bool FB, bool PB, bool TOL = false, bool SELF = false>
 __global__ void __launch_bounds__(kSeqBlock) k_sineosc(float *__restrict__ t_io, uint32_t V, Img out, uint32_t start,
                                                        uint32_t end, float sample_rate, CobP freq, CobP phase) {
     const uint32_t v = blockIdx.x * kSeqBlock + threadIdx.x;
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(kSeqBlock) k_sineosc(float *__restrict__ t_io,
     } else {
         frame_loop<8, ZF, NIN>(out.p, v, out.stride, ins, istr, start, end,
                                [&](uint32_t, const float (&x)[NIN > 0 ? NIN : 1], float &val) ZH_INLINE_LAMBDA {
-            val = o.template frame<FB>(x[0], PB ? x[FB ? 1 : 0] : phase_c);
+            val = o.template frame<FB, 1, SELF>(x[0], PB ? x[FB ? 1 : 0] : phase_c);
             return true;
         });
     }
@@ -1269,7 +1269,7 @@ struct zh_cycle : zh_flipper {
 // One lane per voice walks the span (grid.y == 1, ch = the span, t_in == t_out), or -- few voices, constant speed -- the span as
 // grid.y frame ranges: the walk IS the value (t, t += step, t -= trunc(t)), so a range replays three instructions per earlier
 // frame against the frame's eight issue slots with its `+=` and store; the range that ends the span publishes t.
-template <bool ZF, bool SB>
+template <bool ZF, bool SB, bool SELF = false>
 __global__ void __launch_bounds__(kSeqBlock) k_cycle(const float *__restrict__ t_in, float *__restrict__ t_out, uint32_t V, Img out, uint32_t start,
                                                      uint32_t end, uint32_t ch, float sample_rate, CobP speed) {
     const uint32_t v = blockIdx.x * kSeqBlock + threadIdx.x;
@@ -1289,7 +1289,7 @@ __global__ void __launch_bounds__(kSeqBlock) k_cycle(const float *__restrict__ t
     const float *ins[1] = {SB ? speed.b.p : nullptr};
     const size_t istr[1] = {speed.b.stride};
     frame_loop<8, ZF, SB ? 1 : 0>(out.p, v, out.stride, ins, istr, f0, f1, [&](uint32_t, const float (&x)[1], float &val) ZH_INLINE_LAMBDA {
-        val = o.template frame<SB>(x[0]);
+        val = o.template frame<SB, SELF>(x[0]);
         return true;
     });
     if (f1 == end) t_out[v] = o.t;
@@ -1429,6 +1429,8 @@ int zh_sineosc_paint(zh_sineosc *m, uint32_t start, uint32_t end, const zh_buf *
     if (!p || !cob_ok(p->freq, m->n, end) || !cob_ok(p->phase, m->n, end)) return ZH_ERR_INVALID;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
+    const bool aliased = cob_aliases(p->freq, outputs[0]) || cob_aliases(p->phase, outputs[0]);
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, aliased, flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     const bool tol = (flags & ZH_PAINT_TOLERANT) != 0;                               // the sine in f32 (zmath.hip.h zsinf_tol); the phase walk is exact
     hipStream_t st = m->ctx->stream;
@@ -1439,7 +1441,6 @@ int zh_sineosc_paint(zh_sineosc *m, uint32_t start, uint32_t end, const zh_buf *
     // constant frequency and phase: the replay is two adds a frame, ranges pay up to 4 waves per SIMD at any voice count
     // (24,576 / 32,768 / 65,536 / 131,072 voices: 162 -> 58, 165 -> 68, 174 -> 141, 266 -> 246 us); with a control image the
     // replay re-reads the image (32,768 voices: 166 -> 90 us with 4 ranges, no gain from 65,536 on)
-    const bool aliased = cob_aliases(p->freq, outputs[0]) || cob_aliases(p->phase, outputs[0]);
     const uint32_t ch = end > start && !aliased ? zh_range_frames(m->n, end - start, ZF_SINE_RANGES, fb || pb ? 2048 : 4096, fb || pb ? 65536 : 1u << 20) : 0;
     if (ch) {
         const float *t_in = m->t();
@@ -1459,6 +1460,12 @@ int zh_sineosc_paint(zh_sineosc *m, uint32_t start, uint32_t end, const zh_buf *
 #undef ZH_SINE_R2
         zh_flipper_painted(m);
         m->cur ^= 1;
+        return zh_launch_status();
+    }
+    // the frequency image IS the output image (in_place, tests/test_gpu_views.py): the walk reads each frame's frequency after its own add
+    if (fb && p->freq.buffer.ptr == outputs[0].ptr && p->freq.buffer.stride == outputs[0].stride) {    // (zf is off: zh_zero_first_aliased)
+        if (pb) ZH_LAUNCH((k_sineosc<false, true, true, false, true>), seq_grid(m->n), dim3(kSeqBlock), 0, st, m->t(), m->n, out, start, end, p->sample_rate, f, ph);
+        else ZH_LAUNCH((k_sineosc<false, true, false, false, true>), seq_grid(m->n), dim3(kSeqBlock), 0, st, m->t(), m->n, out, start, end, p->sample_rate, f, ph);
         return zh_launch_status();
     }
 #define ZH_SINE2(FB, PB, TOL)                                                                                       \
@@ -1814,6 +1821,8 @@ int zh_filter_paint(zh_filter *m, uint32_t start, uint32_t end, const zh_buf *ou
         !cob_ok(p->res, m->n, end))
         return ZH_ERR_INVALID;
     if (m->n == 0 || end == start) return ZH_OK;
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]) || cob_aliases(p->cutoff, outputs[0]) ||
+                                    cob_aliases(p->res, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     zh_buf o = outputs[0], in = p->input;
@@ -2032,6 +2041,7 @@ int zh_decimator_paint(zh_decimator *m, uint32_t start, uint32_t end, const zh_b
     if (!p || !buf_covers(p->input, m->n, end)) return ZH_ERR_INVALID;
     if (m->n == 0) return ZH_OK;            // an empty span still resets state when fake >= sample_rate (:37-38)
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     // 4,096 voices: 94 us sequential with per-lane branches, 39 straight-line, 31 as 16 frame ranges (the replay is 8 issue
@@ -2142,6 +2152,7 @@ int zh_cycle_paint(zh_cycle *m, uint32_t start, uint32_t end, const zh_buf *outp
     if (!p || !cob_ok(p->speed, m->n, end)) return ZH_ERR_INVALID;
     if (m->n == 0 || end == start) return ZH_OK;
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, cob_aliases(p->speed, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     Img out = mk_img(outputs[0]);
@@ -2154,7 +2165,10 @@ int zh_cycle_paint(zh_cycle *m, uint32_t start, uint32_t end, const zh_buf *outp
     const float *t_in = m->t();
     float *t_out = chr ? reinterpret_cast<float *>(m->cnt[m->cur ^ 1]) : m->t();
 #define ZH_CYCLE(ZF_, SB_) ZH_LAUNCH((k_cycle<ZF_, SB_>), grid, dim3(kSeqBlock), 0, st, t_in, t_out, m->n, out, start, end, ch, p->sample_rate, sp)
-    if (sb) { if (zf) ZH_CYCLE(true, true); else ZH_CYCLE(false, true); }
+    // the speed image IS the output image (in_place, tests/test_gpu_views.py): each frame's speed is read after its own add
+    if (sb && p->speed.buffer.ptr == outputs[0].ptr && p->speed.buffer.stride == outputs[0].stride)    // (zf is off: zh_zero_first_aliased)
+        ZH_LAUNCH((k_cycle<false, true, true>), grid, dim3(kSeqBlock), 0, st, t_in, t_out, m->n, out, start, end, ch, p->sample_rate, sp);
+    else if (sb) { if (zf) ZH_CYCLE(true, true); else ZH_CYCLE(false, true); }
     else { if (zf) ZH_CYCLE(true, false); else ZH_CYCLE(false, false); }
 #undef ZH_CYCLE
     if (chr) { zh_flipper_painted(m); m->cur ^= 1; }
@@ -2245,6 +2259,7 @@ int zh_distortion_paint(zh_distortion *m, uint32_t start, uint32_t end, const zh
     if (rc) return rc;
     if (!p || p->type > ZH_DISTORTION_CLIP || !buf_covers(p->input, m->n, end)) return ZH_ERR_INVALID;
     if (m->n == 0 || end == start) return ZH_OK;
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const uint32_t chunks = (end - start + DIST_FC - 1) / DIST_FC;

@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(256) k_div_image(Img q, CImg x, uint32_t V, ui
     }
     for (; f < f1; f++, qp += q.stride, xp += x.stride) *qp = *xp / d;
 }
-template <bool ZF, bool QUOT>
+template <bool ZF, bool QUOT, bool SELF = false>
 __global__ void __launch_bounds__(kSeqBlock) k_trisawosc_ctrl(const float *__restrict__ t_in, float *__restrict__ t_out, uint32_t V, Img out,
                                                               uint32_t start, uint32_t end, uint32_t ch, float sample_rate,
                                                               CImg freq_b, F32P color_p) {
@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(kSeqBlock) k_trisawosc_ctrl(const float *__res
     const float *ins[1] = {freq_b.p};
     const size_t istr[1] = {freq_b.stride};
     frame_loop<8, ZF, 1>(out.p, v, out.stride, ins, istr, f0, f1, [&](uint32_t, const float (&x)[1], float &val) ZH_INLINE_LAMBDA {
-        val = QUOT ? o.frame_ctrl_q(x[0]) : o.frame_ctrl(x[0]);
+        val = QUOT ? o.frame_ctrl_q(x[0]) : o.template frame_ctrl<SELF>(x[0]);
         return true;
     });
     if (f1 == end) {
@@ -656,7 +656,6 @@ static int pulseosc_paint_n(zh_pulseosc *m, uint32_t start, uint32_t end, const 
     if (rc) return rc;
     if (m->n == 0 || end == start || nb == 0) return ZH_OK;
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
-    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     if (p->freq.tag == ZH_COB_CONSTANT) {
         launch_osc_const<PulseOscP>(m, outputs, nb, start, end, p->sample_rate, p->freq.constant, p->color, flags);
@@ -679,6 +678,9 @@ static int pulseosc_paint_n(zh_pulseosc *m, uint32_t start, uint32_t end, const 
             // 32,768 voices on); ZH_PULSE_CTRL_SUMS=0: every range replays the frames before it
             const long sums = zh_form(ZF_PULSE_CTRL_SUMS);
             const uint32_t *part = chr && sums && m->part && grid.y <= 64 ? m->part : nullptr;
+            uint32_t fl = flags;                                // (each buffer of a batch is a paint of its own: zero, then paint)
+            if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[b], m->n, bufs_alias(p->freq.buffer, outputs[b]), fl))) return rc;
+            const bool zf = fl & ZH_PAINT_ZERO_FIRST;
             if (part) ZH_LAUNCH(k_pulseosc_ctrl_sums, grid, dim3(kSeqBlock), 0, st, m->part, m->n, start, end, ch, srf, sr8, mk_cimg(p->freq.buffer));
             if (zf) ZH_LAUNCH(k_pulseosc_ctrl<true>, grid, dim3(kSeqBlock), 0, st, ci, co, m->n, out, start, end, ch, srf, sr8, mk_cimg(p->freq.buffer), col, part);
             else ZH_LAUNCH(k_pulseosc_ctrl<false>, grid, dim3(kSeqBlock), 0, st, ci, co, m->n, out, start, end, ch, srf, sr8, mk_cimg(p->freq.buffer), col, part);
@@ -746,7 +748,6 @@ static int trisawosc_paint_n(zh_trisawosc *m, uint32_t start, uint32_t end, cons
     if (rc) return rc;
     if (m->n == 0 || end == start || nb == 0) return ZH_OK;
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
-    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     if (p->freq.tag == ZH_COB_CONSTANT) {
         launch_osc_const<TriSawOscP>(m, outputs, nb, start, end, p->sample_rate, p->freq.constant, p->color, flags);
@@ -781,8 +782,14 @@ static int trisawosc_paint_n(zh_trisawosc *m, uint32_t start, uint32_t end, cons
             float *to = chr ? m->t_next : m->t;
             const uint32_t ch = chr ? chr : end - start;
             const dim3 grid((m->n + kSeqBlock - 1) / kSeqBlock, chr ? (end - start + chr - 1) / chr : 1);
+            uint32_t fl = flags;                                // (each buffer of a batch is a paint of its own: zero, then paint)
+            if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[b], m->n, bufs_alias(p->freq.buffer, outputs[b]), fl))) return rc;
+            const bool zf = fl & ZH_PAINT_ZERO_FIRST;
 #define ZH_TSC(ZF_, Q_) ZH_LAUNCH((k_trisawosc_ctrl<ZF_, Q_>), grid, dim3(kSeqBlock), 0, st, m->t, to, m->n, out, start, end, ch, p->sample_rate, fimg, mk_f32(p->color))
-            if (zf) { if (quot) ZH_TSC(true, true); else ZH_TSC(true, false); }
+            // the frequency image IS this output image (in_place, tests/test_gpu_views.py): each frame's frequency is read after its own add
+            if (p->freq.buffer.ptr == outputs[b].ptr && p->freq.buffer.stride == outputs[b].stride)     // (zf, chr and quot are off: it aliases)
+                ZH_LAUNCH((k_trisawosc_ctrl<false, false, true>), grid, dim3(kSeqBlock), 0, st, m->t, to, m->n, out, start, end, ch, p->sample_rate, fimg, mk_f32(p->color));
+            else if (zf) { if (quot) ZH_TSC(true, true); else ZH_TSC(true, false); }
             else { if (quot) ZH_TSC(false, true); else ZH_TSC(false, false); }
 #undef ZH_TSC
             if (chr) ZH_LAUNCH(k_commit_f32, dim3((m->n + 255) / 256), dim3(256), 0, st, m->t, m->t_next, m->n);

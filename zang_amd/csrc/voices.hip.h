@@ -29,9 +29,10 @@ struct SineOscLane {
         t_step = freq_const / sample_rate;                            // :44 (unused when freq is a buffer)
         inv_sr = 1.0f / sample_rate;                                  // :66
     }
-    template <bool FB, int SINMODE = 1> __device__ __forceinline__ float frame(float freq_i, float phase_i) {
+    // SELF: the frequency image IS the output image -- the reference adds to output[i] and THEN reads freq[i] (:72-73), the sum
+    template <bool FB, int SINMODE = 1, bool SELF = false> __device__ __forceinline__ float frame(float freq_i, float phase_i) {
         const float val = sine_osc_sin<SINMODE>(t + phase_i);
-        if (FB) t += freq_i * inv_sr; else t += t_step;
+        if (FB) t += (SELF ? freq_i + val : freq_i) * inv_sr; else t += t_step;
         return val;
     }
     __device__ __forceinline__ void end() { t = t - truncf(t); }      // :40
@@ -169,9 +170,10 @@ struct TriSawOscLane {
         sample_rate = sr;
         saw = color < 0.25f || color > 0.75f;                         // :137-150
     }
-    __device__ __forceinline__ float frame_ctrl(float s_freq) {
+    // SELF: the frequency image IS the output image -- the reference reads freq[i] after it has added to output[i] (:150-151)
+    template <bool SELF = false> __device__ __forceinline__ float frame_ctrl(float s_freq) {
         const float val = trisaw_naive(t, saw);
-        t += s_freq / sample_rate;
+        t += (SELF ? s_freq + val : s_freq) / sample_rate;
         return val;
     }
     __device__ __forceinline__ float frame_ctrl_q(float q) {         // frame_ctrl with q = s_freq / sample_rate computed beforehand
@@ -414,9 +416,10 @@ struct CycleLane {
         step = speed_const / sample_rate;                             // :37
         isr = 1.0f / sample_rate;                                     // :48
     }
-    template <bool SB> __device__ __forceinline__ float frame(float speed_i) {
+    // SELF: the speed image IS the output image -- the reference reads speed[i] after it has added to outputs[0][i] (:52-53)
+    template <bool SB, bool SELF = false> __device__ __forceinline__ float frame(float speed_i) {
         const float val = t;                                          // :41
-        if (SB) t += speed_i * isr; else t += step;                   // :42 / :53
+        if (SB) t += (SELF ? speed_i + val : speed_i) * isr; else t += step;   // :42 / :53
         t -= truncf(t);                                               // :43
         return val;
     }
