@@ -628,8 +628,8 @@ ZH_API int zh_nice_paint_spans(zh_nice *m, uint32_t span_start, uint32_t span_en
  *   zh_delay           = SimpleDelay   (examples/modules.zig:341-386): out += ring; ring = input
  *   zh_filtered_echoes = FilteredEchoes (examples/modules.zig:390-461): feedback*ring + input -> low-pass -> out, ring
  * The reference moves data in chunks of <= delay_samples (read, then write); reading a slot always precedes
- * writing it, so the per-sample form used by the kernels is equivalent.  StereoEchoes (:463-525) is the host-level
- * composition addInto / zh_delay / zh_filtered_echoes / zh_delay. */
+ * writing it, so the per-sample form used by the kernels is equivalent.  StereoEchoes (:463-525) is zh_stereo_echoes
+ * below: the same composition as one kernel. */
 typedef struct zh_delay zh_delay;
 typedef struct zh_delay_params { zh_buf input; } zh_delay_params;                                     /* :345-347 */
 ZH_API int zh_delay_create(zh_ctx *ctx, uint32_t n_voices, uint32_t delay_samples, zh_delay **out);   /* init(): ring zeros, index 0 */
@@ -651,6 +651,36 @@ ZH_API int zh_filtered_echoes_set_state(zh_filtered_echoes *m, const float *ring
 ZH_API int zh_filtered_echoes_paint(zh_filtered_echoes *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
                                     const zh_buf *temps /*[2], unused; may be NULL*/, zh_bool note_id_changed,
                                     const zh_filtered_echoes_params *params, uint32_t flags);
+
+/* ---------------------------------------------------------------- StereoEchoes(MAIN_DELAY) (examples/modules.zig:464-525)
+ * The bus effect of example_delay.zig / example_detuned.zig as ONE kernel: the dry input into both outputs, SimpleDelay(HALF)
+ * into a zeroed temp, FilteredEchoes(MAIN) on that temp, its output into the left channel and through a second SimpleDelay(HALF)
+ * into the right; HALF = main_delay / 2 (:465).  Per frame, in the reference's order of f32 operations:
+ *   L += x; R += x; t0 = 0 + ring0; ring0 = x; t1 = FilteredEchoes' frame on (ring_e, t0); ring_e = t1;
+ *   L += 0 + t1; R += ring1; ring1 = 0 + t1
+ * Bit-identical to the composition of the calls above.  State per voice: the rings delay0 and delay1 (HALF samples), the ring
+ * echoes (MAIN samples) with its filter (l, b), and one index per ring.  reset() clears the three delays, not the filter
+ * (:488-492, :408-410).  get_state / set_state take each ring as zh_delay_get_state does; an index that is not below its ring's
+ * length is ZH_ERR_INVALID.
+ * paint: outputs[0] = left, outputs[1] = right; the four temps of the reference are not needed.  ZH_PAINT_ZERO_FIRST starts both
+ * outputs from +0 without reading them.  Images may be views (any stride >= n_voices, any 4-byte aligned base).  No two of input,
+ * outputs[0] and outputs[1] may share memory: ZH_ERR_INVALID (column ranges of one allocation with one stride do not; views of
+ * different strides whose extents intersect count as sharing).  main_delay < 2 is ZH_ERR_INVALID at create; ZH_PAINT_TOLERANT is
+ * ZH_ERR_UNSUPPORTED.  A paint neither allocates nor synchronises.  Up to the table's stereo_echoes_pc_max voices with main_delay >= 192
+ * and a span of at least 64 frames: loader / filter / writer waves per 64 voices (k_stereo_echoes_pc); otherwise one lane per
+ * voice (k_stereo_echoes). */
+typedef struct zh_stereo_echoes zh_stereo_echoes;
+typedef struct zh_stereo_echoes_params { zh_buf input; zh_f32 feedback_volume; zh_f32 cutoff; } zh_stereo_echoes_params;   /* :470-474 */
+ZH_API int zh_stereo_echoes_create(zh_ctx *ctx, uint32_t n_voices, uint32_t main_delay, zh_stereo_echoes **out);
+ZH_API int zh_stereo_echoes_destroy(zh_stereo_echoes *m);
+ZH_API int zh_stereo_echoes_reset(zh_stereo_echoes *m);
+ZH_API int zh_stereo_echoes_get_state(zh_stereo_echoes *m, float *rings0_voice_major, uint32_t *index0, float *rings1_voice_major, uint32_t *index1,
+                                      float *rings_e_voice_major, uint32_t *index_e, zh_filter_state *filter);
+ZH_API int zh_stereo_echoes_set_state(zh_stereo_echoes *m, const float *rings0_voice_major, const uint32_t *index0, const float *rings1_voice_major,
+                                      const uint32_t *index1, const float *rings_e_voice_major, const uint32_t *index_e, const zh_filter_state *filter);
+ZH_API int zh_stereo_echoes_paint(zh_stereo_echoes *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                                  const zh_buf *temps /*[4], unused; may be NULL*/, zh_bool note_id_changed,
+                                  const zh_stereo_echoes_params *params, uint32_t flags);
 
 /* ---------------------------------------------------------------- Noise -> Filter voice (examples/example_stereo.zig:71-82)
  * zero(temp); Noise.paint(temp); Filter.paint(out, input = temp, type, cutoff, res) as ONE kernel: the

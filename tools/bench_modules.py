@@ -92,6 +92,9 @@ if V <= 16384:
     m = mod.FilteredEchoes(V, 600, ctx); case("FilteredEchoes(600), ZH_PAINT_TOLERANT (two pieces)", m, lambda o, m=m: m.paint(span, [o], [], False, m.Params(inp, 0.6, 0.1), zero_first=True, tolerant=True), 3)
     m = mod.FilteredEchoes(V, 15000, ctx); case("FilteredEchoes(15000)", m, lambda o, m=m: m.paint(span, [o], [], False, m.Params(inp, 0.6, 0.1), zero_first=True), 3)
     m = mod.FilteredEchoes(V, 15000, ctx); case("FilteredEchoes(15000), ZH_PAINT_TOLERANT", m, lambda o, m=m: m.paint(span, [o], [], False, m.Params(inp, 0.6, 0.1), zero_first=True, tolerant=True), 3)
+# two outputs: `o` of the output ring is the left one, out_r the right; zero-first the paint moves 36 B per voice-sample (reads = 8)
+out_r = ctx.image(F, V)
+m = mod.StereoEchoes(V, 15000, ctx); case("StereoEchoes(15000)", m, lambda o, m=m: m.paint(span, [o, out_r], None, False, m.Params(inp, 0.6, 0.1), zero_first=True), 8)
 crv = torch.tensor([[0.0, 0.0], [1.0, 0.005], [0.3, 0.012], [0.8, 0.02], [0.0, 0.05]], dtype=torch.float32, device=dev)
 m = mod.Curve(V, ctx)
 _crv_k = [0]

@@ -49,6 +49,10 @@ MODULES = [
     ("filtered_echoes", "FilteredEchoes", 2, "examples/modules.zig:390-461", [("delay_samples", "u32")]),
     ("noise_filter", "NoiseFilter", 1, "examples/example_stereo.zig:71-82", [("first_seed", "u64")]),
 ]
+# modules with two outputs, same tuple: StereoEchoes sits on the output bus (left, right)
+STEREO_MODULES = [
+    ("stereo_echoes", "StereoEchoes", 4, "examples/modules.zig:464-525", [("main_delay", "u32")]),
+]
 HOST_MODULES = ["sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate", "filter", "sampler", "decimator", "distortion"]
 # pointer parameters that address MANY elements (everything else of struct type points at one)
 MANY_NAMES = {"outputs", "temps", "host", "filter", "impulses"}
@@ -207,7 +211,7 @@ def zig_type(ctype, model, name="", func="", field=False):
     raise SystemExit(f"gen_zig_binding: no Zig type for C type '{ctype}' ({func} {name})")
 
 
-WRAPPED = {"zh_" + k for k, *_ in MODULES}
+WRAPPED = {"zh_" + k for k, *_ in MODULES + STEREO_MODULES}
 
 
 def opaque_name(c):
@@ -286,6 +290,8 @@ const std = @import("std");
     w(HELPERS)
     for key, zname, ntemps, ref, extra in MODULES:
         w(emit_module(model, structs, key, zname, ntemps, ref, extra))
+    for key, zname, ntemps, ref, extra in STEREO_MODULES:
+        w(emit_module(model, structs, key, zname, ntemps, ref, extra, num_outputs=2))
     w("// ---------------------------------------------------------------- literal one-voice drop-ins (host []f32 slices)")
     w(HOST_HELPERS)
     for key in HOST_MODULES:
@@ -380,7 +386,7 @@ def params_fields(model, structs, sname):
     return out
 
 
-def emit_module(model, structs, key, zname, ntemps, ref, extra):
+def emit_module(model, structs, key, zname, ntemps, ref, extra, num_outputs=1):
     h = opaque_name("zh_" + key)
     P = camel(f"zh_{key}_params")
     fields = params_fields(model, structs, f"zh_{key}_params")
@@ -390,7 +396,7 @@ def emit_module(model, structs, key, zname, ntemps, ref, extra):
     a = L.append
     a(f"/// `{zname}` ({ref}) for a batch of n voices on the GPU.")
     a(f"pub const {zname} = struct {{")
-    a("    pub const num_outputs = 1;")
+    a(f"    pub const num_outputs = {num_outputs};")
     a(f"    pub const num_temps = {ntemps};")
     a("    pub const Params = struct {")
     for f, t in fields:

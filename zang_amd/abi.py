@@ -134,6 +134,10 @@ class FilteredEchoesParams(C.Structure):
     _fields_ = [("input", Buf), ("feedback_volume", F32), ("cutoff", F32)]
 
 
+class StereoEchoesParams(C.Structure):
+    _fields_ = [("input", Buf), ("feedback_volume", F32), ("cutoff", F32)]
+
+
 class NoiseFilterParams(C.Structure):
     _fields_ = [("color", u32), ("type", u32), ("cutoff", F32), ("res", F32)]
 
@@ -480,6 +484,12 @@ SIGNATURES = {
     "zh_filtered_echoes_get_state": (C.c_int, [vp, vp, vp, vp]),
     "zh_filtered_echoes_set_state": (C.c_int, [vp, vp, vp, vp]),
     "zh_filtered_echoes_paint": (C.c_int, _paint(FilteredEchoesParams)),
+    "zh_stereo_echoes_create": (C.c_int, [vp, u32, u32, P(vp)]),
+    "zh_stereo_echoes_destroy": (C.c_int, [vp]),
+    "zh_stereo_echoes_reset": (C.c_int, [vp]),
+    "zh_stereo_echoes_get_state": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "zh_stereo_echoes_set_state": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "zh_stereo_echoes_paint": (C.c_int, _paint(StereoEchoesParams)),
     "zh_noise_filter_create": (C.c_int, [vp, u32, u64, P(vp)]),
     "zh_noise_filter_destroy": (C.c_int, [vp]),
     "zh_noise_filter_get_state": (C.c_int, [vp, vp]),

@@ -201,6 +201,56 @@ __global__ void __launch_bounds__(kSeqBlock) k_filtered_echoes(DelayState d, flo
     l_io[v] = l; b_io[v] = b;
 }
 
+// The filter wave of the two role-wave pipelines below (k_filtered_echoes_pc, k_stereo_echoes_pc): at step c it fetches tile c - 1 of
+// the filter's input from LDS while it runs the state-variable recurrence over tile c - 2 out of registers and hands (l, b) of every
+// frame on.  Two steps per iteration where the arrays alternate between steps, so that they keep their registers; a __syncthreads
+// ends every step (the other two waves run the same count).
+template <uint32_t CH>
+__device__ __forceinline__ void echoes_filter_wave(float4 (*in_q)[CH / 4][64], float4 (*l_q)[CH / 4][64], float4 (*b_q)[CH / 4][64], uint32_t lane,
+                                                   uint32_t n, uint32_t nchunks, float &l, float &b, float cut, float res) {
+    constexpr uint32_t Q = CH / 4;
+    const uint32_t last = nchunks + 2;
+    auto frames = [&](uint32_t c) ZH_INLINE_LAMBDA { return c < nchunks ? min(CH, n - c * CH) : 0u; };
+    auto at = [&](float4 (*t)[64], uint32_t k) ZH_INLINE_LAMBDA -> float & { return reinterpret_cast<float *>(&t[k >> 2][lane])[k & 3]; };
+    float4 fa[Q], fb[Q];                                              // the tile in hand / the next one
+#pragma unroll
+    for (uint32_t q = 0; q < Q; q++) fa[q] = fb[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    auto step = [&](uint32_t c, float4 (&cur)[Q], float4 (&nxt)[Q]) ZH_INLINE_LAMBDA {
+        if (c == 0 || c > nchunks + 1) return;
+        const float4 (*tn)[64] = in_q[(c - 1) & 1];                  // (complete only if that tile is a whole one: otherwise unused)
+#pragma unroll
+        for (uint32_t q = 0; q < Q; q++) nxt[q] = tn[q][lane];
+        if (c == 1) return;
+        const uint32_t dd = c - 2, nf = frames(dd);
+        float4 (*tl)[64] = l_q[dd & 1], (*tb)[64] = b_q[dd & 1];
+        if (nf == CH) {
+#pragma unroll
+            for (uint32_t q = 0; q < Q; q++) {
+                const SvfOut s0 = svf_core(l, b, cur[q].x, cut, res);
+                const SvfOut s1 = svf_core(l, b, cur[q].y, cut, res);
+                const SvfOut s2 = svf_core(l, b, cur[q].z, cut, res);
+                const SvfOut s3 = svf_core(l, b, cur[q].w, cut, res);
+                tl[q][lane] = make_float4(s0.l, s1.l, s2.l, s3.l);     // (h is not needed: dsp.hip.h svf_lowpass_into_zero)
+                tb[q][lane] = make_float4(s0.b, s1.b, s2.b, s3.b);
+            }
+        } else {                                                      // (the last tile: the loader has stopped, its buffer stays)
+            float4 (*ti)[64] = in_q[dd & 1];
+            for (uint32_t k = 0; k < nf; k++) {
+                const SvfOut sv = svf_core(l, b, at(ti, k), cut, res);
+                at(tl, k) = sv.l; at(tb, k) = sv.b;
+            }
+        }
+    };
+    for (uint32_t c = 0; c <= last; c += 2) {
+        step(c, fa, fb);
+        __syncthreads();
+        if (c + 1 <= last) {
+            step(c + 1, fb, fa);
+            __syncthreads();
+        }
+    }
+}
+
 // FilteredEchoes at a small voice count, delay >= 192 frames: three waves per 64 voices (the form of modules.hip's
 // k_filter_pc: float4 LDS tiles, per-role step loops).  Wave 0 requests a tile's ring slots and input rows two tiles ahead and
 // forms the filter's input (in = ((0 + delayed) * feedback + x) + fcdcoffset); wave 1 runs the state-variable recurrence alone
@@ -298,43 +348,7 @@ __global__ void __launch_bounds__(192) k_filtered_echoes_pc(DelayState d, float 
         if (live) d.index[v] = slot_of(n);
     } else if (role == 1) {
         float l = l_io[vc], b = b_io[vc];
-        float4 fa[Q], fb[Q];                                          // the tile in hand / the next one
-#pragma unroll
-        for (uint32_t q = 0; q < Q; q++) fa[q] = fb[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        auto step = [&](uint32_t c, float4 (&cur)[Q], float4 (&nxt)[Q]) ZH_INLINE_LAMBDA {
-            if (c == 0 || c > nchunks + 1) return;
-            const float4 (*tn)[64] = in_q[(c - 1) & 1];              // (complete only if that tile is a whole one: otherwise unused)
-#pragma unroll
-            for (uint32_t q = 0; q < Q; q++) nxt[q] = tn[q][lane];
-            if (c == 1) return;
-            const uint32_t dd = c - 2, nf = frames(dd);
-            float4 (*tl)[64] = l_q[dd & 1], (*tb)[64] = b_q[dd & 1];
-            if (nf == CH) {
-#pragma unroll
-                for (uint32_t q = 0; q < Q; q++) {
-                    const SvfOut s0 = svf_core(l, b, cur[q].x, cut, res);
-                    const SvfOut s1 = svf_core(l, b, cur[q].y, cut, res);
-                    const SvfOut s2 = svf_core(l, b, cur[q].z, cut, res);
-                    const SvfOut s3 = svf_core(l, b, cur[q].w, cut, res);
-                    tl[q][lane] = make_float4(s0.l, s1.l, s2.l, s3.l);     // (h is not needed: dsp.hip.h svf_lowpass_into_zero)
-                    tb[q][lane] = make_float4(s0.b, s1.b, s2.b, s3.b);
-                }
-            } else {                                                  // (the last tile: the loader has stopped, its buffer stays)
-                float4 (*ti)[64] = in_q[dd & 1];
-                for (uint32_t k = 0; k < nf; k++) {
-                    const SvfOut sv = svf_core(l, b, at(ti, k), cut, res);
-                    at(tl, k) = sv.l; at(tb, k) = sv.b;
-                }
-            }
-        };
-        for (uint32_t c = 0; c <= last; c += 2) {
-            step(c, fa, fb);
-            __syncthreads();
-            if (c + 1 <= last) {
-                step(c + 1, fb, fa);
-                __syncthreads();
-            }
-        }
+        echoes_filter_wave<CH>(in_q, l_q, b_q, lane, n, nchunks, l, b, cut, res);
         if (live) { l_io[v] = l; b_io[v] = b; }
     } else {
         float bn[CH];                                                 // the output rows of the tile after the one in hand
@@ -520,6 +534,267 @@ __global__ void __launch_bounds__(256) k_fe_tp_b(const FeTpArgs a) {
             fe_tp_tiles<!ZF>(a, v, idx0, a.start, a.end, body);
             leave();
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- StereoEchoes
+// StereoEchoes(MAIN).paint, examples/modules.zig:494-523, as one kernel: the dry input into both outputs, delay0 (HALF = MAIN / 2)
+// into a zeroed temp, FilteredEchoes(MAIN) on that temp into another zeroed temp, that one into the left output and through
+// delay1 (HALF) into the right.  Per frame, in the reference's order of f32 operations:
+//   L = L + x; R = R + x                                   (:503-504)
+//   t0 = 0 + ring0; ring0 = x                              (:507-510)
+//   t1 = FilteredEchoes' frame on (ringE, t0); ringE = t1  (:512-517; `one` of k_filtered_echoes)
+//   e = 0 + t1 (the zeroed temps[1]); L = L + e            (:519)
+//   R = R + ring1; ring1 = e                               (:520-522)
+// Each of the three rings is read before it is written within a frame and a slot is next touched a ring length later, so the
+// sample walk equals the reference's chunked read-then-write form ring by ring, as for the two modules above.
+struct StereoState { DelayState d0, d1, de; float *l, *b; };   // delay0, delay1 (HALF samples each), echoes (MAIN) and its filter
+struct zh_stereo_echoes { zh_ctx *ctx; StereoState s; };
+
+__device__ __forceinline__ float se_filter_input(float ring_e, float ring_0, float feedback) {
+    float t0 = 0.0f + ring_e;                                         // zero(temp0); readDelayBuffer (:425-428)
+    t0 = t0 * feedback;                                               // multiplyWithScalar (:433)
+    return t0 + (0.0f + ring_0);                                      // addInto (:436) of delay0's zeroed output (:507-510)
+}
+
+// lane = voice.  CH = 8: a chunk's loads ahead of its stores (HALF >= 8: the eight frames touch eight different slots of every ring)
+template <bool ZF, uint32_t CH>
+__global__ void __launch_bounds__(kSeqBlock) k_stereo_echoes(StereoState s, Img outL, Img outR, CImg input, uint32_t start, uint32_t end,
+                                                             F32P feedback_p, F32P cutoff_p) {
+    const uint32_t v = blockIdx.x * kSeqBlock + threadIdx.x, V = s.de.n;
+    if (v >= V) return;
+    const float feedback = feedback_p.get(v);
+    const float cut = zclampf(cutoff_p.get(v), 0.0f, 1.0f);           // Filter.zig:114
+    const float res = 1.0f - zclampf(0.0f, 0.0f, 1.0f);               // res = constant(0.0) (:441) -> Filter.zig:118
+    const uint32_t DH = s.d0.delay_samples, DE = s.de.delay_samples;
+    uint32_t i0 = s.d0.index[v], i1 = s.d1.index[v], ie = s.de.index[v];
+    float l = s.l[v], b = s.b[v];
+    float *ring0 = s.d0.ring + v, *ring1 = s.d1.ring + v, *ringE = s.de.ring + v;
+    float *oL = outL.at(start, v), *oR = outR.at(start, v);
+    const float *in = input.at(start, v);
+    auto echo = [&](float re, float r0) ZH_INLINE_LAMBDA {
+        const SvfOut sv = svf_step(l, b, se_filter_input(re, r0, feedback), cut, res);   // Filter.paint low_pass (Filter.zig:135-146)
+        return svf_lowpass_into_zero(sv.l, sv.b);                     // zero(temp1); += (:439)
+    };
+    uint32_t i = start;
+    if constexpr (CH > 1)
+    for (; i + CH <= end; i += CH, oL += CH * outL.stride, oR += CH * outR.stride, in += CH * input.stride) {
+        float *p0[CH], *p1[CH], *pe[CH];
+        float r0[CH], r1[CH], re[CH], x[CH], bl[CH], br[CH], t1[CH];
+#pragma unroll
+        for (uint32_t k = 0; k < CH; k++) {
+            p0[k] = ring0 + (size_t)i0 * V; p1[k] = ring1 + (size_t)i1 * V; pe[k] = ringE + (size_t)ie * V;
+            i0 = delay_next<CH>(i0, DH); i1 = delay_next<CH>(i1, DH); ie = delay_next<CH>(ie, DE);
+            r0[k] = *p0[k]; r1[k] = *p1[k]; re[k] = *pe[k];
+            x[k] = in[(size_t)k * input.stride];
+            bl[k] = ZF ? 0.0f : oL[(size_t)k * outL.stride];
+            br[k] = ZF ? 0.0f : oR[(size_t)k * outR.stride];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < CH; k++) t1[k] = echo(re[k], r0[k]);
+#pragma unroll
+        for (uint32_t k = 0; k < CH; k++) {
+            const float e = 0.0f + t1[k];
+            store_row(oL + (size_t)k * outL.stride, (bl[k] + x[k]) + e);
+            store_row(oR + (size_t)k * outR.stride, (br[k] + x[k]) + r1[k]);
+            *p0[k] = x[k]; *pe[k] = t1[k]; *p1[k] = e;
+        }
+    }
+    for (; i < end; i++, oL += outL.stride, oR += outR.stride, in += input.stride) {
+        float *p0 = ring0 + (size_t)i0 * V, *p1 = ring1 + (size_t)i1 * V, *pe = ringE + (size_t)ie * V;
+        const float x = *in, r1 = *p1;
+        const float t1 = echo(*pe, *p0);
+        const float e = 0.0f + t1;
+        store_row(oL, ((ZF ? 0.0f : *oL) + x) + e);
+        store_row(oR, ((ZF ? 0.0f : *oR) + x) + r1);
+        *p0 = x; *pe = t1; *p1 = e;
+        i0 = delay_next<CH>(i0, DH); i1 = delay_next<CH>(i1, DH); ie = delay_next<CH>(ie, DE);
+    }
+    s.d0.index[v] = i0; s.d1.index[v] = i1; s.de.index[v] = ie;
+    s.l[v] = l; s.b[v] = b;
+}
+
+// Few voices (row stereo_echoes_pc_max of the table), MAIN >= 192 (HALF >= 96): the three role waves of k_filtered_echoes_pc per 64 voices, 32-frame tiles.  Wave 0 (loader)
+// owns delay0: it requests a tile's echo-ring slots, delay0 slots and input rows two tiles ahead, forms the filter's input
+// (((0 + ringE) * feedback + (0 + ring0)) + fcdcoffset) and stores the tile's inputs into delay0.  Wave 1 carries the filter's
+// (l, b) alone.  Wave 2 (writer) owns delay1 and the outputs: it forms t1, stores L, R, the echo ring and delay1, three tiles
+// behind the loader, with the next tile's input rows, delay1 slots and output rows requested a step ahead.
+// Why every slot is stored before the wave that reads it asks for it (step c: loader publishes tile c and requests tile c + 2,
+// writer stores tile c - 3; a __syncthreads ends every step):
+//  - echo ring (writer stores, loader reads): frame j reads what frame j - MAIN stored.  The frames of tile c + 2 are at most
+//    32 (c + 3) - 1, so their sources are at most 32 (c + 3) - 1 - 192 = 32 (c - 3) - 1: tile c - 4 or earlier, stored in step
+//    c - 1 or earlier, a barrier before the request.  The slots the writer fills meanwhile (tile c - 3) lie 129..191 < MAIN
+//    frames before the requested ones: never the same slot.
+//  - delay0 (loader stores at publish, loader reads at request): the sources of tile c + 2 are at most 32 (c + 3) - 1 - 96 =
+//    32 c - 1: tile c - 1 or earlier, stored by this same wave in step c - 1 or earlier, ahead of the request in program order
+//    (a wave's accesses to one address keep their order).  The slots of tile c + 2 are first rewritten at publish(c + 2),
+//    after their request.
+//  - delay1 (writer stores tile c - 3, then requests tile c - 2): sources at most 32 (c - 1) - 1 - 96 = 32 (c - 4) - 1: tile
+//    c - 5 or earlier, stored by this wave two steps before.
+//  - a partial (last) tile is read frame by frame at its own step, later than a request would have been.
+// Same operations on the same values as k_stereo_echoes => same bits.
+template <bool ZF>
+__global__ void __launch_bounds__(192) k_stereo_echoes_pc(StereoState s, Img outL, Img outR, CImg input, uint32_t start, uint32_t end,
+                                                          F32P feedback_p, F32P cutoff_p) {
+    constexpr uint32_t CH = 32, Q = CH / 4;
+    __shared__ float4 in_q[2][Q][64], l_q[2][Q][64], b_q[2][Q][64];
+    const uint32_t lane = threadIdx.x & 63, role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // 0 loader, 1 filter, 2 writer
+    const uint32_t V = s.de.n, v = blockIdx.x * 64 + lane;
+    const bool live = v < V;
+    const uint32_t vc = live ? v : V - 1;
+    const uint32_t n = end - start, nchunks = (n + CH - 1) / CH;
+    const float feedback = feedback_p.get(vc);
+    const float cut = zclampf(cutoff_p.get(vc), 0.0f, 1.0f);          // Filter.zig:114
+    const float res = 1.0f - zclampf(0.0f, 0.0f, 1.0f);               // res = constant(0.0) (:441) -> Filter.zig:118
+    auto frames = [&](uint32_t c) ZH_INLINE_LAMBDA { return c < nchunks ? min(CH, n - c * CH) : 0u; };
+    auto at = [&](float4 (*t)[64], uint32_t k) ZH_INLINE_LAMBDA -> float & { return reinterpret_cast<float *>(&t[k >> 2][lane])[k & 3]; };
+    const uint32_t voff = vc * 4u, rrow = V * 4u, irow = (uint32_t)input.stride * 4u, lrow = (uint32_t)outL.stride * 4u, rrow_out = (uint32_t)outR.stride * 4u;
+    // one ring as a wave sees it: the slot of the span's frame j, and whether a tile's 32 slots are consecutive ring rows for every
+    // lane (the voices share one index and the tile does not wrap: k_filtered_echoes_pc)
+    struct Ring {
+        float *p; uint32_t i0, D; bool uni;
+        __device__ __forceinline__ uint32_t slot(uint32_t j) const { return (uint32_t)(((uint64_t)i0 + j) % D); }
+        __device__ __forceinline__ bool rows(uint32_t j) const { return uni && (uint32_t)__builtin_amdgcn_readfirstlane((int)slot(j)) + 32u <= D; }
+    };
+    auto ring_of = [&](const DelayState &d) ZH_INLINE_LAMBDA {
+        Ring r; r.p = d.ring + vc; r.i0 = d.index[vc]; r.D = d.delay_samples;
+        r.uni = __builtin_amdgcn_ballot_w64(r.i0 != (uint32_t)__builtin_amdgcn_readfirstlane((int)r.i0)) == 0;
+        return r;
+    };
+    // a whole tile of one ring into registers / out of registers
+    auto ring_load = [&](const Ring &r, float *ringbase, uint32_t j, float (&dst)[CH]) ZH_INLINE_LAMBDA {
+        if (r.rows(j)) {
+            const zh_rsrc_t rr = zrow_rsrc(ringbase, V, (uint32_t)__builtin_amdgcn_readfirstlane((int)r.slot(j)));
+#pragma unroll
+            for (uint32_t k = 0; k < CH; k++) dst[k] = zrow_load<1>(rr, voff, k * rrow);
+        } else {
+            uint32_t sl = r.slot(j);
+#pragma unroll
+            for (uint32_t k = 0; k < CH; k++) { dst[k] = r.p[(size_t)sl * V]; sl = sl + 1 == r.D ? 0 : sl + 1; }
+        }
+    };
+    auto ring_store = [&](const Ring &r, float *ringbase, uint32_t j, const float (&src)[CH]) ZH_INLINE_LAMBDA {
+        if (r.rows(j)) {
+            const zh_rsrc_t rr = zrow_rsrc(ringbase, V, (uint32_t)__builtin_amdgcn_readfirstlane((int)r.slot(j)));
+            if (live) {
+#pragma unroll
+                for (uint32_t k = 0; k < CH; k++) zrow_store<1>(rr, voff, k * rrow, src[k]);
+            }
+        } else {
+            uint32_t sl = r.slot(j);
+#pragma unroll
+            for (uint32_t k = 0; k < CH; k++) { if (live) r.p[(size_t)sl * V] = src[k]; sl = sl + 1 == r.D ? 0 : sl + 1; }
+        }
+    };
+    const uint32_t last = nchunks + 2;
+    if (role == 0) {
+        const Ring re = ring_of(s.de), r0 = ring_of(s.d0);
+        float ea[CH], za[CH], xa[CH], eb[CH], zb[CH], xb[CH];         // echo-ring slots, delay0 slots and input rows of the tiles c (even / odd), then c + 2
+        auto request = [&](uint32_t c, float (&en)[CH], float (&zn)[CH], float (&xn)[CH]) ZH_INLINE_LAMBDA {
+            if (frames(c) != CH) return;
+            const zh_rsrc_t ri = zrow_rsrc(input.p, input.stride, start + c * CH);
+#pragma unroll
+            for (uint32_t k = 0; k < CH; k++) xn[k] = zrow_load<1>(ri, voff, k * irow);
+            ring_load(re, s.de.ring, c * CH, en);
+            ring_load(r0, s.d0.ring, c * CH, zn);
+        };
+        auto in_of = [&](float e, float z) ZH_INLINE_LAMBDA { return se_filter_input(e, z, feedback) + kSvfDcOffset; };   // Filter.zig:135
+        auto publish = [&](uint32_t c, float (&en)[CH], float (&zn)[CH], float (&xn)[CH]) ZH_INLINE_LAMBDA {
+            const uint32_t nf = frames(c);
+            float4 (*t)[64] = in_q[c & 1];
+            if (nf == CH) {
+#pragma unroll
+                for (uint32_t q = 0; q < Q; q++)
+                    t[q][lane] = make_float4(in_of(en[4 * q], zn[4 * q]), in_of(en[4 * q + 1], zn[4 * q + 1]), in_of(en[4 * q + 2], zn[4 * q + 2]), in_of(en[4 * q + 3], zn[4 * q + 3]));
+                ring_store(r0, s.d0.ring, c * CH, xn);                // delay0: ring = input (:510)
+            } else {
+                uint32_t se = re.slot(c * CH), s0 = r0.slot(c * CH);
+                const float *ip = input.at(start + c * CH, vc);
+                for (uint32_t k = 0; k < nf; k++) {
+                    float *p0 = r0.p + (size_t)s0 * V;
+                    const float x = ip[(size_t)k * input.stride];
+                    at(t, k) = in_of(re.p[(size_t)se * V], *p0);
+                    if (live) *p0 = x;
+                    se = se + 1 == re.D ? 0 : se + 1; s0 = s0 + 1 == r0.D ? 0 : s0 + 1;
+                }
+            }
+            request(c + 2, en, zn, xn);
+        };
+        request(0, ea, za, xa); request(1, eb, zb, xb);
+        for (uint32_t c = 0; c <= last; c += 2) {
+            if (c < nchunks) publish(c, ea, za, xa);
+            __syncthreads();
+            if (c + 1 <= last) {
+                if (c + 1 < nchunks) publish(c + 1, eb, zb, xb);
+                __syncthreads();
+            }
+        }
+        if (live) { s.de.index[v] = re.slot(n); s.d0.index[v] = r0.slot(n); }
+    } else if (role == 1) {
+        float l = s.l[vc], b = s.b[vc];
+        echoes_filter_wave<CH>(in_q, l_q, b_q, lane, n, nchunks, l, b, cut, res);
+        if (live) { s.l[v] = l; s.b[v] = b; }
+    } else {
+        const Ring re = ring_of(s.de), r1 = ring_of(s.d1);
+        float xn[CH], dn[CH], ln[CH], rn[CH];                         // input rows, delay1 slots and output rows of the tile after the one in hand
+        for (uint32_t c = 0; c <= last; c++) {
+            if (c > 2) {
+                const uint32_t dd = c - 3, nf = frames(dd);
+                float4 (*tl)[64] = l_q[dd & 1], (*tb)[64] = b_q[dd & 1];
+                if (nf == CH) {
+                    float t1[CH], e[CH];
+#pragma unroll
+                    for (uint32_t q = 0; q < Q; q++) {
+                        const float4 xl = tl[q][lane], xb = tb[q][lane];
+                        t1[4 * q] = svf_lowpass_into_zero(xl.x, xb.x); t1[4 * q + 1] = svf_lowpass_into_zero(xl.y, xb.y);   // zero(temp1); += low-pass (:439, Filter.zig:146)
+                        t1[4 * q + 2] = svf_lowpass_into_zero(xl.z, xb.z); t1[4 * q + 3] = svf_lowpass_into_zero(xl.w, xb.w);
+                    }
+                    const zh_rsrc_t rl = zrow_rsrc(outL.p, outL.stride, start + dd * CH), rr = zrow_rsrc(outR.p, outR.stride, start + dd * CH);
+#pragma unroll
+                    for (uint32_t k = 0; k < CH; k++) {
+                        e[k] = 0.0f + t1[k];                          // addInto(temps[1], temp1) on the zeroed temps[1] (:512, :448)
+                        if (live) {
+                            zrow_store<1>(rl, voff, k * lrow, ((ZF ? 0.0f : ln[k]) + xn[k]) + e[k]);        // (:503, :519)
+                            zrow_store<1>(rr, voff, k * rrow_out, ((ZF ? 0.0f : rn[k]) + xn[k]) + dn[k]);   // (:504, :520)
+                        }
+                    }
+                    ring_store(re, s.de.ring, dd * CH, t1);           // writeDelayBuffer(temp1) (:452)
+                    ring_store(r1, s.d1.ring, dd * CH, e);            // delay1: ring = temps[1] (:520-522)
+                } else {
+                    float *pl = outL.at(start + dd * CH, vc), *pr = outR.at(start + dd * CH, vc);
+                    const float *ip = input.at(start + dd * CH, vc);
+                    uint32_t se = re.slot(dd * CH), s1 = r1.slot(dd * CH);
+                    for (uint32_t k = 0; k < nf; k++) {
+                        const float t1 = svf_lowpass_into_zero(at(tl, k), at(tb, k));
+                        const float e = 0.0f + t1, x = ip[(size_t)k * input.stride];
+                        float *p1 = r1.p + (size_t)s1 * V;
+                        if (live) {
+                            const float d1 = *p1;
+                            float *ql = pl + (size_t)k * outL.stride, *qr = pr + (size_t)k * outR.stride;
+                            *ql = ((ZF ? 0.0f : *ql) + x) + e;
+                            *qr = ((ZF ? 0.0f : *qr) + x) + d1;
+                            re.p[(size_t)se * V] = t1;
+                            *p1 = e;
+                        }
+                        se = se + 1 == re.D ? 0 : se + 1; s1 = s1 + 1 == r1.D ? 0 : s1 + 1;
+                    }
+                }
+            }
+            if (c >= 2 && frames(c - 2) == CH) {                      // the rows of the tile written at the next step
+                const uint32_t j = (c - 2) * CH;
+                const zh_rsrc_t ri = zrow_rsrc(input.p, input.stride, start + j);
+#pragma unroll
+                for (uint32_t k = 0; k < CH; k++) xn[k] = zrow_load<1>(ri, voff, k * irow);
+                ring_load(r1, s.d1.ring, j, dn);
+                if (!ZF) {
+                    const zh_rsrc_t rl = zrow_rsrc(outL.p, outL.stride, start + j), rr = zrow_rsrc(outR.p, outR.stride, start + j);
+#pragma unroll
+                    for (uint32_t k = 0; k < CH; k++) { ln[k] = zrow_load<1>(rl, voff, k * lrow); rn[k] = zrow_load<1>(rr, voff, k * rrow_out); }
+                }
+            }
+            __syncthreads();
+        }
+        if (live) s.d1.index[v] = r1.slot(n);
     }
 }
 
@@ -709,6 +984,107 @@ int zh_filtered_echoes_paint(zh_filtered_echoes *m, uint32_t start, uint32_t end
     if (flags & ZH_PAINT_ZERO_FIRST) { if (chunked) ZH_FE(true, 8); else ZH_FE(true, 1); }
     else { if (chunked) ZH_FE(false, 8); else ZH_FE(false, 1); }
 #undef ZH_FE
+    return zh_launch_status();
+}
+
+// ---- StereoEchoes
+static void stereo_free(StereoState &s) { delay_free(s.d0); delay_free(s.d1); delay_free(s.de); (void)hipFree(s.l); (void)hipFree(s.b); }
+int zh_stereo_echoes_create(zh_ctx *ctx, uint32_t n, uint32_t main_delay, zh_stereo_echoes **out) { ZH_GUARD(ctx);
+    if (!ctx || !out || main_delay < 2) return ZH_ERR_INVALID;        // HALF = main_delay / 2 (:465) must be a Delay that makes progress
+    zh_stereo_echoes *m = new (std::nothrow) zh_stereo_echoes();
+    if (!m) return ZH_ERR_INVALID;
+    m->ctx = ctx; m->s.l = m->s.b = nullptr;
+    m->s.d0 = m->s.d1 = m->s.de = DelayState{nullptr, nullptr, n, 0};
+    int rc = delay_alloc(ctx, m->s.d0, n, main_delay / 2);
+    if (!rc) rc = delay_alloc(ctx, m->s.d1, n, main_delay / 2);
+    if (!rc) rc = delay_alloc(ctx, m->s.de, n, main_delay);
+    if (!rc) rc = dev_alloc(&m->s.l, n);
+    if (!rc) rc = dev_alloc(&m->s.b, n);
+    if (!rc && n) rc = (int)hipMemsetAsync(m->s.l, 0, (size_t)n * 4, ctx->stream);   // Filter.init()
+    if (!rc && n) rc = (int)hipMemsetAsync(m->s.b, 0, (size_t)n * 4, ctx->stream);
+    if (rc) { stereo_free(m->s); delete m; return rc; }
+    *out = m;
+    return ZH_OK;
+}
+int zh_stereo_echoes_destroy(zh_stereo_echoes *m) { ZH_GUARD(m ? m->ctx : nullptr);
+    if (!m) return ZH_ERR_INVALID;
+    (void)hipStreamSynchronize(m->ctx->stream);
+    stereo_free(m->s);
+    delete m;
+    return ZH_OK;
+}
+int zh_stereo_echoes_reset(zh_stereo_echoes *m) { ZH_GUARD(m ? m->ctx : nullptr);   // :488-492: the three delays; the filter keeps its state (:408-410)
+    if (!m) return ZH_ERR_INVALID;
+    int rc = delay_reset(m->ctx, m->s.d0);
+    if (!rc) rc = delay_reset(m->ctx, m->s.d1);
+    if (!rc) rc = delay_reset(m->ctx, m->s.de);
+    return rc;
+}
+int zh_stereo_echoes_get_state(zh_stereo_echoes *m, float *rings0, uint32_t *index0, float *rings1, uint32_t *index1,
+                               float *rings_e, uint32_t *index_e, zh_filter_state *filter) { ZH_GUARD(m ? m->ctx : nullptr);
+    if (!m || !filter) return ZH_ERR_INVALID;
+    int rc = delay_get(m->ctx, m->s.d0, rings0, index0);
+    if (!rc) rc = delay_get(m->ctx, m->s.d1, rings1, index1);
+    if (!rc) rc = delay_get(m->ctx, m->s.de, rings_e, index_e);
+    if (rc) return rc;
+    const uint32_t n = m->s.de.n;
+    std::vector<float> l(n), b(n);
+    rc = zh_download(m->ctx, l.data(), m->s.l, (size_t)n * 4);
+    if (!rc) rc = zh_download(m->ctx, b.data(), m->s.b, (size_t)n * 4);
+    if (rc) return rc;
+    for (uint32_t v = 0; v < n; v++) filter[v] = zh_filter_state{l[v], b[v]};
+    return ZH_OK;
+}
+int zh_stereo_echoes_set_state(zh_stereo_echoes *m, const float *rings0, const uint32_t *index0, const float *rings1, const uint32_t *index1,
+                               const float *rings_e, const uint32_t *index_e, const zh_filter_state *filter) { ZH_GUARD(m ? m->ctx : nullptr);
+    if (!m || !filter || !rings0 || !index0 || !rings1 || !index1 || !rings_e || !index_e) return ZH_ERR_INVALID;
+    const uint32_t n = m->s.de.n;
+    for (uint32_t v = 0; v < n; v++)                                  // every index is checked before anything is uploaded
+        if (index0[v] >= m->s.d0.delay_samples || index1[v] >= m->s.d1.delay_samples || index_e[v] >= m->s.de.delay_samples) return ZH_ERR_INVALID;
+    int rc = delay_set(m->ctx, m->s.d0, rings0, index0);
+    if (!rc) rc = delay_set(m->ctx, m->s.d1, rings1, index1);
+    if (!rc) rc = delay_set(m->ctx, m->s.de, rings_e, index_e);
+    if (rc) return rc;
+    std::vector<float> l(n), b(n);
+    for (uint32_t v = 0; v < n; v++) { l[v] = filter[v].l; b[v] = filter[v].b; }
+    rc = zh_upload(m->ctx, m->s.l, l.data(), (size_t)n * 4);
+    if (!rc) rc = zh_upload(m->ctx, m->s.b, b.data(), (size_t)n * 4);
+    return rc;
+}
+// do two views of n voices share a float?  With equal strides the rows of one lie at a fixed column offset inside the rows of the
+// other, so column ranges of one allocation are told apart; views of different strides whose extents intersect count as overlapping.
+static bool views_overlap(const zh_buf &a, const zh_buf &b, uint32_t n) {
+    if (!bufs_alias(a, b)) return false;
+    if (a.stride != b.stride) return true;
+    const uintptr_t S = a.stride, pa = (uintptr_t)a.ptr / sizeof(float), pb = (uintptr_t)b.ptr / sizeof(float);
+    const uintptr_t d = pb >= pa ? (pb - pa) % S : (S - (pa - pb) % S) % S;
+    return d < n || d + n > S;
+}
+int zh_stereo_echoes_paint(zh_stereo_echoes *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                           zh_bool note_id_changed, const zh_stereo_echoes_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    (void)temps; (void)note_id_changed;                               // the four temps of the reference stay in registers
+    if (!m || !outputs || !p || end < start) return ZH_ERR_INVALID;
+    const uint32_t n = m->s.de.n;
+    if (!buf_covers(outputs[0], n, end) || !buf_covers(outputs[1], n, end) || !buf_covers(p->input, n, end)) return ZH_ERR_INVALID;
+    // the fused order of reads and writes is not the composition's: no two of the three images may share memory
+    if (views_overlap(outputs[0], outputs[1], n) || views_overlap(p->input, outputs[0], n) || views_overlap(p->input, outputs[1], n)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (n == 0 || end == start) return ZH_OK;
+    const dim3 grid_pc((n + 63) / 64);
+#define ZH_SE_ARGS m->ctx->stream, m->s, mk_img(outputs[0]), mk_img(outputs[1]), mk_cimg(p->input), start, end, mk_f32(p->feedback_volume), mk_f32(p->cutoff)
+    // (a span of at least two 32-frame tiles, as zh_filtered_echoes_paint asks: the pipeline takes tiles + 3 barrier steps, so a
+    // shorter span would be all fill and drain where the walk does its frames in one pass)
+    if (n <= (uint32_t)zh_form(ZF_STEREO_ECHOES_PC_MAX) && m->s.de.delay_samples >= 192 && end - start >= 64) {
+        if (flags & ZH_PAINT_ZERO_FIRST) ZH_LAUNCH(k_stereo_echoes_pc<true>, grid_pc, dim3(192), 0, ZH_SE_ARGS);
+        else ZH_LAUNCH(k_stereo_echoes_pc<false>, grid_pc, dim3(192), 0, ZH_SE_ARGS);
+        return zh_launch_status();
+    }
+    const bool chunked = m->s.d0.delay_samples >= 8;
+#define ZH_SE(ZF_, CH_) ZH_LAUNCH((k_stereo_echoes<ZF_, CH_>), seq_grid(n), dim3(kSeqBlock), 0, ZH_SE_ARGS)
+    if (flags & ZH_PAINT_ZERO_FIRST) { if (chunked) ZH_SE(true, 8); else ZH_SE(true, 1); }
+    else { if (chunked) ZH_SE(false, 8); else ZH_SE(false, 1); }
+#undef ZH_SE
+#undef ZH_SE_ARGS
     return zh_launch_status();
 }
 

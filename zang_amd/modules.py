@@ -569,6 +569,62 @@ class FilteredEchoes(_Module):
         self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_TOLERANT if tolerant else 0)
 
 
+class StereoEchoes(_Module):
+    """examples/modules.zig:464-525 as one kernel: the dry input to both outputs, SimpleDelay(main_delay / 2), FilteredEchoes(main_delay)
+    to the left, a second SimpleDelay(main_delay / 2) to the right.  outputs = [left, right]; the reference's four temps are not needed.
+    Input and the two outputs must not share memory."""
+    _prefix = "stereo_echoes"
+    num_outputs = 2
+    num_temps = 4
+
+    @dataclass
+    class Params:
+        input: Any
+        feedback_volume: Any
+        cutoff: Any
+
+    def __init__(self, n_voices, main_delay, ctx=None):
+        self.main_delay = int(main_delay)
+        self.half_delay = self.main_delay // 2
+        super().__init__(n_voices, ctx, C.c_uint32(self.main_delay))
+
+    @classmethod
+    def init(cls, n_voices, main_delay, ctx=None):
+        return cls(n_voices, main_delay, ctx)
+
+    def reset(self):
+        """the three delays; the filter keeps its state (:488-492, :408-410)"""
+        abi.check(self.lib.zh_stereo_echoes_reset(self.handle), "zh_stereo_echoes_reset")
+
+    def state(self):
+        """(rings0, idx0, rings1, idx1, rings_e, idx_e, filter): rings voice-major [n_voices][ring length]"""
+        n = self.n_voices
+        r0 = np.zeros((n, self.half_delay), np.float32); r1 = np.zeros((n, self.half_delay), np.float32)
+        re = np.zeros((n, self.main_delay), np.float32)
+        i0, i1, ie = (np.zeros(n, np.uint32) for _ in range(3))
+        flt = np.zeros(n, dtype=np.dtype(abi.FilterState))
+        abi.check(self.lib.zh_stereo_echoes_get_state(self.handle, r0.ctypes.data, i0.ctypes.data, r1.ctypes.data, i1.ctypes.data,
+                                                      re.ctypes.data, ie.ctypes.data, flt.ctypes.data), "zh_stereo_echoes_get_state")
+        return r0, i0, r1, i1, re, ie, flt
+
+    def set_state(self, rings0, idx0, rings1, idx1, rings_e, idx_e, flt):
+        n = self.n_voices
+        r0 = np.ascontiguousarray(rings0, np.float32); r1 = np.ascontiguousarray(rings1, np.float32)
+        re = np.ascontiguousarray(rings_e, np.float32)
+        assert r0.shape == r1.shape == (n, self.half_delay) and re.shape == (n, self.main_delay)
+        i0, i1, ie = (np.ascontiguousarray(i, np.uint32) for i in (idx0, idx1, idx_e))
+        assert i0.shape == i1.shape == ie.shape == (n,)
+        flt = np.ascontiguousarray(flt, dtype=np.dtype(abi.FilterState))
+        assert flt.shape == (n,)
+        abi.check(self.lib.zh_stereo_echoes_set_state(self.handle, r0.ctypes.data, i0.ctypes.data, r1.ctypes.data, i1.ctypes.data,
+                                                      re.ctypes.data, ie.ctypes.data, flt.ctypes.data), "zh_stereo_echoes_set_state")
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, tolerant=False):
+        """tolerant=True is refused (ZH_ERR_UNSUPPORTED): the module has exact forms only."""
+        cp = abi.StereoEchoesParams(as_buf(params.input), as_f32(params.feedback_volume), as_f32(params.cutoff))
+        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.PAINT_TOLERANT if tolerant else 0)
+
+
 class NoiseFilter(_Module):
     """Noise -> Filter as one fused kernel (examples/example_stereo.zig:71-82; BASELINE config 3)."""
     _prefix = "noise_filter"
