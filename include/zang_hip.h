@@ -1006,6 +1006,41 @@ ZH_API int zh_voice_bank_get_state(zh_voice_bank *bank, zh_voice_bank_instrument
 ZH_API int zh_voice_bank_set_state(zh_voice_bank *bank, const zh_voice_bank_instrument_state *instruments,
                                    const zh_voice_bank_voice_state *voices);
 
+/* LIVE voice banks: the same tables from impulses pushed from outside (Notes(T).ImpulseQueue, notes.zig:72-128, as
+ * examples/example_polyphony2.zig:61-95 uses it) instead of a song.  A live bank has no song; every call of
+ * zh_voice_bank_schedule_live schedules ONE buffer [0, out_len) from one batch of pushes over all instruments, in push order:
+ * per instrument exactly zh_impulse_queue_push for each of its entries in batch order, zh_impulse_queue_consume,
+ * zh_polyphony_dispatcher_dispatch, then zh_trigger_counter(0, out_len) and zh_trigger_next per slot -- in one kernel
+ * (k_voice_bank_schedule_live), bit for bit.  So: a push is dropped when 32 of that instrument are accepted in this call or when
+ * its frame is below the last accepted one's; an accepted one takes event_id = next_event_id++ (per instrument, from 1, kept
+ * across calls; zh_voice_bank_reset clears the dispatcher and the Triggers and leaves it alone: ImpulseQueue has no reset).
+ * Where the reference says "not sure what would happen", what that composition gives: an impulse whose frame is >= out_len is
+ * accepted, takes an event id and its slot in the dispatcher, ends a carried note at out_len like any later impulse, and is never
+ * painted (the next call does not see it; the note the Trigger carries on is the one before it); out_len == 0 does the same for
+ * every impulse of the call and emits no sub-span.  A Trigger's carried note is kept as its record (the batch is gone by the
+ * next call).  Sub-span frames are relative to the buffer; counts start from 0 every call.
+ * The call validates, sorts the batch by instrument on the host (stable), copies it through pinned staging owned by the bank
+ * (a ring; the call waits only for a slot whose copy is still in flight) and enqueues one copy and one launch: no stream
+ * synchronise, and the caller's arrays may be reused on return.  batch == NULL or n == 0: no pushes (carried notes still paint).
+ * ZH_ERR_INVALID: a song bank here or a live bank in zh_voice_bank_schedule / _get_state / _set_state, an instrument index
+ * >= n_instruments, batch->n > max_impulses_per_call, max_spans of 0 or above the capacity.  ZH_ERR_UNSUPPORTED while a capture
+ * records (a replay would read host memory that has since changed).  destroy / reset / reserve / script_table / span_param /
+ * span_table / overflows work as on a song bank; overflow is handled the same way. */
+typedef struct zh_bank_impulses {                                /* host arrays, in push order over all instruments */
+    uint32_t n; const uint32_t *instrument, *frame; const uint64_t *note_id; const void *paramses;   /* [n] each; [n][params_size] */
+} zh_bank_impulses;
+typedef struct zh_voice_bank_live_voice_state {
+    uint32_t used, note_on; uint64_t note_id, event_id;          /* the dispatcher's slot */
+    uint32_t has_note, reserved; uint64_t trigger_note_id;       /* the Trigger's carried note ... */
+    uint32_t carried[16];                                        /* ... and its record (params_size / 4 words; zeros without a note) */
+} zh_voice_bank_live_voice_state;
+ZH_API int zh_voice_bank_create_live(zh_ctx *ctx, uint32_t n_instruments, uint32_t polyphony, uint32_t params_size, uint32_t note_on_offset,
+                                     uint32_t max_impulses_per_call, zh_voice_bank **out);
+ZH_API int zh_voice_bank_schedule_live(zh_voice_bank *bank, uint32_t out_len, uint32_t max_spans, const zh_bank_impulses *batch);
+ZH_API int zh_voice_bank_live_get_state(zh_voice_bank *bank, uint64_t *next_event_id /*[n]*/,
+                                        zh_voice_bank_live_voice_state *voices /*[n * polyphony]*/);
+ZH_API int zh_voice_bank_live_set_state(zh_voice_bank *bank, const uint64_t *next_event_id, const zh_voice_bank_live_voice_state *voices);
+
 /* ---------------------------------------------------------------- single-voice host-pointer wrappers
  * The literal one-voice form of a Zig module call: `state` is the Zig struct (in/out), `outputs[0]` and every
  * input buffer are HOST float[>= span_end] slices exactly like zang's []f32, params are plain values.  Each call

@@ -227,6 +227,73 @@ private:
     }
 };
 
+// A live voice bank (zh_voice_bank_create_live): no song; push() collects impulses on the host as Notes(T).ImpulseQueue.push does
+// (examples/example_polyphony2.zig:80-95), schedule() sends them and enqueues the kernel that takes every instrument through
+// ImpulseQueue -> PolyphonyDispatcher -> Triggers for one buffer.  Views as on VoiceBank.
+template <class Record>
+class LiveVoiceBank {
+    static_assert(sizeof(Record) % 4 == 0 && sizeof(Record) <= ZH_MAX_PARAMS_SIZE, "a record is a multiple of 4 bytes, at most 64");
+    zh_voice_bank *h_ = nullptr;
+    uint32_t n_, polyphony_;
+    std::vector<uint32_t> instrument_, frame_;
+    std::vector<uint64_t> note_id_;
+    std::vector<Record> records_;
+
+public:
+    LiveVoiceBank(Context &ctx, uint32_t n_instruments, uint32_t polyphony, uint32_t note_on_offset, uint32_t max_impulses)
+        : n_(n_instruments), polyphony_(polyphony) {
+        check(zh_voice_bank_create_live(ctx.get(), n_instruments, polyphony, (uint32_t)sizeof(Record), note_on_offset, max_impulses, &h_),
+              "zh_voice_bank_create_live");
+    }
+    ~LiveVoiceBank() { if (h_) zh_voice_bank_destroy(h_); }
+    LiveVoiceBank(const LiveVoiceBank &) = delete;
+    LiveVoiceBank &operator=(const LiveVoiceBank &) = delete;
+    zh_voice_bank *get() const { return h_; }
+    uint32_t instruments() const { return n_; }
+    uint32_t voices() const { return n_ * polyphony_; }
+    void reset() { check(zh_voice_bank_reset(h_), "zh_voice_bank_reset"); }
+    void reserve(uint32_t max_rows) { check(zh_voice_bank_reserve(h_, max_rows), "zh_voice_bank_reserve"); }   // invalidates views
+    void push(uint32_t instrument, uint32_t frame, uint64_t note_id, const Record &record) {
+        instrument_.push_back(instrument); frame_.push_back(frame); note_id_.push_back(note_id); records_.push_back(record);
+    }
+    void schedule(uint32_t out_len, uint32_t max_spans) {          // what was pushed since the last call; the lists are empty afterwards
+        const zh_bank_impulses batch{(uint32_t)instrument_.size(), instrument_.data(), frame_.data(), note_id_.data(), records_.data()};
+        const int rc = zh_voice_bank_schedule_live(h_, out_len, max_spans, batch.n ? &batch : nullptr);
+        instrument_.clear(); frame_.clear(); note_id_.clear(); records_.clear();
+        check(rc, "zh_voice_bank_schedule_live");
+    }
+    zh_script_span_table scriptTable(uint32_t max_spans) const {
+        zh_script_span_table t{};
+        check(zh_voice_bank_script_table(h_, max_spans, &t), "zh_voice_bank_script_table");
+        return t;
+    }
+    zh_script_span_param spanParamF(uint32_t word) const { zh_script_span_param p = spanParam(word); p.u = nullptr; return p; }
+    zh_script_span_param spanParamU(uint32_t word) const { zh_script_span_param p = spanParam(word); p.f = nullptr; return p; }
+    zh_span_table spanTable(uint32_t max_spans, uint32_t freq_word) const {
+        zh_span_table t{};
+        check(zh_voice_bank_span_table(h_, max_spans, freq_word, &t), "zh_voice_bank_span_table");
+        return t;
+    }
+    uint64_t overflows() { uint64_t n = 0; check(zh_voice_bank_overflows(h_, &n), "zh_voice_bank_overflows"); return n; }
+    struct State { std::vector<uint64_t> next_event_id; std::vector<zh_voice_bank_live_voice_state> voices; };
+    State getState() {
+        State s{std::vector<uint64_t>(n_), std::vector<zh_voice_bank_live_voice_state>(voices())};
+        check(zh_voice_bank_live_get_state(h_, s.next_event_id.data(), s.voices.data()), "zh_voice_bank_live_get_state");
+        return s;
+    }
+    void setState(const State &s) {
+        if (s.next_event_id.size() != n_ || s.voices.size() != voices()) throw Error(ZH_ERR_INVALID, "LiveVoiceBank::setState: a state of another bank");
+        check(zh_voice_bank_live_set_state(h_, s.next_event_id.data(), s.voices.data()), "zh_voice_bank_live_set_state");
+    }
+
+private:
+    zh_script_span_param spanParam(uint32_t word) const {
+        zh_script_span_param p{};
+        check(zh_voice_bank_span_param(h_, word, &p), "zh_voice_bank_span_param");
+        return p;
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -5,7 +5,12 @@
   (b) device zh_voice_bank_schedule + the same paint, the tables never leave the device
 Host clock around work that ends in a synchronise; HIP events around the scheduling kernel alone and the paint alone.
     python tools/bank_bench.py [--instruments 16384] [--polyphony 8] [--buffers 50] [--rounds 3] [--song]
---song: the 17 sub-voices of the example song's shape instead (three instruments of polyphony 3, 10 and 4, one bank each)."""
+--song: the 17 sub-voices of the example song's shape instead (three instruments of polyphony 3, 10 and 4, one bank each).
+--live: the scheduling alone when the events are PUSHED per buffer (the impulses the corpus's NoteTrackers deliver), three routes:
+  (a) host   zh_impulse_queue_* -> zh_polyphony_dispatcher_dispatch -> zh_trigger_* per instrument, assemble, upload (from Python: call-bound;
+             (a') is zh_poly_voice_schedule on the same events, one compiled call per instrument: what a compiled composition cannot beat)
+  (b) live   zh_voice_bank_schedule_live: host sort, staging copy and kernel
+  (c) song   zh_voice_bank_schedule on the same events known in advance"""
 import argparse
 import ctypes as C
 import os
@@ -141,6 +146,162 @@ def run(ctx, shapes, buffers, rounds, warmup, seed, out):
         p["host"].close(); p["bank"].close()
 
 
+def run_live(ctx, n, P, buffers, warmup, host_buffers, seed, out):
+    """one buffer of pushed impulses for n instruments, three routes (module docstring); (b)'s tables are checked against (c)'s"""
+    import torch
+    from zang_amd import abi, bank as zbank
+    from zang_amd.spans import SpanTable
+    L = ctx.lib
+    total = warmup + buffers
+    offsets, rec, t, ids = corpus(n, total, 0.004, seed)
+    V = n * P
+    # what the NoteTrackers deliver, per buffer, in time order over all instruments (each instrument's own order kept)
+    trackers, batches = [], [[] for _ in range(total)]
+    for i in range(n):
+        a, z = int(offsets[i]), int(offsets[i + 1])
+        h = C.c_void_p()
+        abi.check(L.zh_note_tracker_create(8, z - a, rec[a:z].ctypes.data, t[a:z].ctypes.data_as(C.POINTER(C.c_float)),
+                                           ids[a:z].ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(h)), "create")
+        trackers.append(h)
+    iap = abi.Iap()
+    for b in range(total):
+        for i, h in enumerate(trackers):
+            if L.zh_note_tracker_consume(h, float(SR), 0, F, C.byref(iap)):
+                raise RuntimeError("zh_note_tracker_consume")
+            k = int(iap.len)
+            assert k < 32
+            if k:
+                imp = np.frombuffer(C.string_at(iap.impulses, k * 24), np.uint64).reshape(k, 3)
+                batches[b].append((np.full(k, i, np.uint32), imp[:, 0].astype(np.uint32), imp[:, 1].copy(), np.frombuffer(C.string_at(iap.paramses, k * 8), REC)))
+    for h in trackers:
+        L.zh_note_tracker_destroy(h)
+    for b in range(total):
+        inst, frame, nid, recs = (np.concatenate(x) for x in zip(*batches[b]))
+        order = np.argsort(frame, kind="stable")
+        batches[b] = tuple(np.ascontiguousarray(x[order]) for x in (inst, frame, nid, recs))
+    most = max(len(x[0]) for x in batches)
+    live = zbank.LiveVoiceBank(ctx, n, P, REC, 4, most, rows=CAP)
+    song = zbank.VoiceBank(ctx, P, rec, offsets, t, ids, 4, rows=CAP)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    stream = ctx._stream
+    res = {"b_call": [], "b_total": [], "b_dev_us": [], "c_total": [], "c_dev_us": []}
+    for b in range(total):
+        inst, frame, nid, recs = batches[b]
+        c = abi.BankImpulses(len(inst), inst.ctypes.data, frame.ctypes.data, nid.ctypes.data, recs.ctypes.data)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ev[0].record(stream)
+        abi.check(L.zh_voice_bank_schedule_live(live.handle, F, CAP, C.byref(c)), "zh_voice_bank_schedule_live")
+        t1 = time.perf_counter()
+        ev[1].record(stream)
+        ctx.sync()
+        t2 = time.perf_counter()
+        dev_b = ev[0].elapsed_time(ev[1]) * 1e3
+        t3 = time.perf_counter()
+        ev[0].record(stream)
+        song.schedule([F], SR, CAP)
+        ev[1].record(stream)
+        ctx.sync()
+        t4 = time.perf_counter()
+        if b >= warmup:
+            res["b_call"].append(t1 - t0); res["b_total"].append(t2 - t0); res["b_dev_us"].append(dev_b)
+            res["c_total"].append(t4 - t3); res["c_dev_us"].append(ev[0].elapsed_time(ev[1]) * 1e3)
+    dl, ds = live.download(CAP), song.download(CAP)
+    K = int(ds["count"].max())
+    m = np.arange(K, dtype=np.uint32)[:, None] < ds["count"][None, :]
+    assert np.array_equal(dl["count"], ds["count"]) and all(np.array_equal(dl[k][:K][m], ds[k][:K][m]) for k in ("start", "end", "note_on", "note_id_changed"))
+    assert all(np.array_equal(dl["words"][w][:K][m], ds["words"][w][:K][m]) for w in range(2)) and live.overflows() == 0 and song.overflows() == 0
+    # (a): the host classes from Python, per instrument; (a'): one compiled call per instrument on the same events
+    queues, disps, trigs = [], [], []
+    for i in range(n):
+        q, d = C.c_void_p(), C.c_void_p()
+        abi.check(L.zh_impulse_queue_create(8, C.byref(q)), "create"); abi.check(L.zh_polyphony_dispatcher_create(P, 8, 4, C.byref(d)), "create")
+        ts = []
+        for _ in range(P):
+            h = C.c_void_p()
+            abi.check(L.zh_trigger_create(8, C.byref(h)), "create")
+            ts.append(h)
+        queues.append(q); disps.append(d); trigs.append(ts)
+    poly, ps = (abi.Iap * P)(), abi.PaintSpan()
+    push, consume, dispatch, counter, nxt = L.zh_impulse_queue_push, L.zh_impulse_queue_consume, L.zh_polyphony_dispatcher_dispatch, L.zh_trigger_counter, L.zh_trigger_next
+    a_parts = []
+    for b in range(min(host_buffers + 1, total)):
+        inst, frame, nid, recs = batches[b]
+        count = np.zeros(V, np.uint32)
+        start = np.zeros((CAP, V), np.uint32); end = np.zeros((CAP, V), np.uint32); freq = np.zeros((CAP, V), np.float32)
+        on = np.zeros((CAP, V), np.uint8); nic = np.zeros((CAP, V), np.uint8)
+        t0 = time.perf_counter()
+        base = recs.ctypes.data
+        for k in range(len(inst)):
+            push(queues[inst[k]], int(frame[k]), int(nid[k]), base + 8 * k)
+        for i in range(n):
+            consume(queues[i], C.byref(iap))
+            dispatch(disps[i], iap, poly)
+            for s in range(P):
+                v = i * P + s
+                counter(trigs[i][s], 0, F, poly[s])
+                r = 0
+                while nxt(trigs[i][s], C.byref(ps)) == 1:
+                    start[r, v] = ps.start; end[r, v] = ps.end; nic[r, v] = ps.note_id_changed
+                    freq[r, v] = np.frombuffer(ps.params, np.float32, 1)[0]; on[r, v] = ps.params[4]
+                    r += 1
+                count[v] = r
+        t1 = time.perf_counter()
+        K = max(int(count.max()), 1)
+        SpanTable.from_arrays(count, start[:K], end[:K], freq[:K], on[:K], nic[:K], ctx.device)
+        ctx.sync()
+        t2 = time.perf_counter()
+        if b >= 1:
+            a_parts.append((t1 - t0, t2 - t1))
+    assert np.array_equal(count, song_count_at(ctx, n, P, offsets, rec, t, ids, min(host_buffers + 1, total)))
+    for q in queues:
+        L.zh_impulse_queue_destroy(q)
+    for d in disps:
+        L.zh_polyphony_dispatcher_destroy(d)
+    for ts in trigs:
+        for h in ts:
+            L.zh_trigger_destroy(h)
+    host = HostRoute(L, ctx, P, offsets, rec, t, ids, None)
+    a2 = []
+    for b in range(total):
+        t0 = time.perf_counter()
+        f, frp, sr = L.zh_poly_voice_schedule, host.fr.ctypes.data, float(SR)
+        for h, c_, s_, e_, r_, n_ in host.args:
+            if f(h, sr, frp, 1, CAP, c_, s_, e_, r_, n_):
+                raise RuntimeError("zh_poly_voice_schedule")
+        t1 = time.perf_counter()
+        cnt = host.count.reshape(V)
+        K = max(int(cnt.max()), 1)
+        tr = lambda a: np.ascontiguousarray(a[:, :K].transpose(1, 0, 2)).reshape(K, V)
+        SpanTable.from_arrays(cnt, tr(host.start), tr(host.end), tr(host.rec["freq"]), tr(host.rec["on"]), tr(host.nic), ctx.device)
+        ctx.sync()
+        t2 = time.perf_counter()
+        if b >= warmup:
+            a2.append((t1 - t0, t2 - t1))
+    host.close()
+    live.close(); song.close()
+    ap, a2p = np.median(np.array(a_parts), axis=0) * 1e3, np.median(np.array(a2), axis=0) * 1e3
+    med = lambda k, scale=1e3: float(np.median(res[k]) * scale)
+    print(f"live: {n} instruments x polyphony {P} = {V} voices, one buffer of {F} frames, {int(np.mean([len(x[0]) for x in batches]))} impulses per buffer, "
+          f"{buffers} buffers per route ({len(a_parts)} for (a)); (b) and (c) left identical tables", file=out)
+    print(f"  (a)  host classes from Python  median {ap.sum():9.3f} ms/buffer = composition {ap[0]:.3f} + assemble/upload {ap[1]:.3f}", file=out)
+    print(f"  (a') zh_poly_voice_schedule    median {a2p.sum():9.3f} ms/buffer = schedule calls {a2p[0]:.3f} + assemble/upload {a2p[1]:.3f}", file=out)
+    print(f"  (b)  zh_voice_bank_schedule_live median {med('b_total'):7.3f} ms/buffer to the end of the kernel: the call (sort, staging, enqueue) {med('b_call'):.3f}, "
+          f"HIP events around the call (they see the host sort too) {med('b_dev_us', 1):.1f} us (min {np.min(res['b_dev_us']):.1f})", file=out)
+    print(f"  (c)  zh_voice_bank_schedule    median {med('c_total'):9.3f} ms/buffer, kernel by HIP events {med('c_dev_us', 1):.1f} us (min {np.min(res['c_dev_us']):.1f})", file=out, flush=True)
+
+
+def song_count_at(ctx, n, P, offsets, rec, t, ids, n_buffers):
+    """the song bank's counts after n_buffers buffers (what (a)'s last buffer must have produced)"""
+    from zang_amd import bank as zbank
+    b = zbank.VoiceBank(ctx, P, rec, offsets, t, ids, 4, rows=CAP)
+    for _ in range(n_buffers):
+        b.schedule([F], SR, CAP)
+    c = b.download(CAP)["count"]
+    b.close()
+    return c
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--instruments", type=int, default=16384)
@@ -150,9 +311,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20261016)
     ap.add_argument("--song", action="store_true")
+    ap.add_argument("--live", action="store_true")
+    ap.add_argument("--host-buffers", type=int, default=3, help="--live: buffers of route (a), after one warm-up buffer")
     a = ap.parse_args()
     import zang_amd
     ctx = zang_amd.default_context()
+    if a.live:
+        run_live(ctx, a.instruments, a.polyphony, a.buffers, a.warmup, a.host_buffers, a.seed, sys.stdout)
+        return
     shapes = [(1, 3), (1, 10), (1, 4)] if a.song else [(a.instruments, a.polyphony)]
     run(ctx, shapes, a.buffers, a.rounds, a.warmup, a.seed, sys.stdout)
 

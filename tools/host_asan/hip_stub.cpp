@@ -59,6 +59,9 @@ hipError_t hipFree(void *p) {
     free(p);
     return hipSuccess;
 }
+// pinned host memory: plain host memory here, tracked like the device's so that a leak or a double free shows
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return hipMalloc(p, n); }
+hipError_t hipHostFree(void *p) { return hipFree(p); }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { FakeStream *fs = new FakeStream(); g_streams.insert(fs); *s = reinterpret_cast<hipStream_t>(fs); return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { FakeStream *fs = S(s); if (!fs) return hipErrorInvalidValue; if (fs->capturing) die("a capturing stream destroyed"); g_streams.erase(fs); delete fs; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t s) { FakeStream *fs = S(s); if (fs && fs->capturing) die("hipStreamSynchronize on a capturing stream (it would invalidate the capture)"); return hipSuccess; }
@@ -126,6 +129,7 @@ hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t s) {
     return hipSuccess;
 }
 hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new FakeEvent()); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<FakeEvent *>(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t s) { (void)S(s); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }

@@ -247,6 +247,15 @@ class VoiceBankVoiceState(C.Structure):          # zh_voice_bank_voice_state
                 ("trigger_note_id", u64), ("trigger_event", u64)]
 
 
+class BankImpulses(C.Structure):                 # zh_bank_impulses
+    _fields_ = [("n", u32), ("instrument", vp), ("frame", vp), ("note_id", vp), ("paramses", vp)]
+
+
+class VoiceBankLiveVoiceState(C.Structure):      # zh_voice_bank_live_voice_state
+    _fields_ = [("used", u32), ("note_on", u32), ("note_id", u64), ("event_id", u64), ("has_note", u32), ("reserved", u32),
+                ("trigger_note_id", u64), ("carried", u32 * 16)]
+
+
 class HCob(C.Structure):
     _fields_ = [("tag", u32), ("constant", f32), ("buffer", C.POINTER(f32))]
 
@@ -443,6 +452,10 @@ SIGNATURES = {
     "zh_voice_bank_overflows": (C.c_int, [vp, P(u64)]),
     "zh_voice_bank_get_state": (C.c_int, [vp, P(VoiceBankInstrumentState), P(VoiceBankVoiceState)]),
     "zh_voice_bank_set_state": (C.c_int, [vp, P(VoiceBankInstrumentState), P(VoiceBankVoiceState)]),
+    "zh_voice_bank_create_live": (C.c_int, [vp, u32, u32, u32, u32, u32, P(vp)]),
+    "zh_voice_bank_schedule_live": (C.c_int, [vp, u32, u32, P(BankImpulses)]),
+    "zh_voice_bank_live_get_state": (C.c_int, [vp, P(u64), P(VoiceBankLiveVoiceState)]),
+    "zh_voice_bank_live_set_state": (C.c_int, [vp, P(u64), P(VoiceBankLiveVoiceState)]),
     "zh_zscript_compile": (C.c_int, [C.c_char_p, C.c_char_p, u32, P(vp), C.c_char_p, C.c_size_t]),
     "zh_zscript_destroy": (C.c_int, [vp]),
     "zh_zscript_free_text": (None, [vp]),

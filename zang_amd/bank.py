@@ -127,3 +127,55 @@ class VoiceBank:
             self.close()
         except Exception:       # noqa: BLE001
             pass
+
+
+class LiveVoiceBank(VoiceBank):
+    """A bank without a song (zh_voice_bank_create_live): impulses are pushed from outside, as into the reference's ImpulseQueue, and
+    every schedule() call takes what was pushed since the last one through ImpulseQueue -> PolyphonyDispatcher -> Triggers for one
+    buffer, in one kernel.  `record_dtype`: the note params as a numpy structured dtype (itemsize a multiple of 4, at most 64);
+    `max_impulses`: the most pushes one schedule() may carry.  Views, reserve, reset, overflows, download and close as on VoiceBank."""
+
+    def __init__(self, ctx, n_instruments, polyphony, record_dtype, note_on_offset, max_impulses, rows=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.polyphony, self.n_instruments = polyphony, n_instruments
+        self.n_voices = n_instruments * polyphony
+        self.record_dtype = np.dtype(record_dtype)
+        self.params_size = self.record_dtype.itemsize
+        self.max_impulses = max_impulses
+        self._pushed = ([], [], [], [])
+        self.handle = C.c_void_p()
+        abi.check(self.lib.zh_voice_bank_create_live(ctx.handle, n_instruments, polyphony, self.params_size, note_on_offset, max_impulses,
+                                                     C.byref(self.handle)), "zh_voice_bank_create_live")
+        ctx._children.add(self)
+        if rows is not None:
+            self.reserve(rows)
+
+    def push(self, instrument, frame, note_id, record):
+        """ImpulseQueue.push for one instrument (scalars), or for many at once (equal-length arrays, in push order)"""
+        for acc, x in zip(self._pushed, (np.atleast_1d(np.asarray(instrument, np.uint32)), np.atleast_1d(np.asarray(frame, np.uint32)),
+                                         np.atleast_1d(np.asarray(note_id, np.uint64)), np.atleast_1d(np.asarray(record, self.record_dtype)))):
+            acc.append(x)
+        if not len(self._pushed[0][-1]) == len(self._pushed[1][-1]) == len(self._pushed[2][-1]) == len(self._pushed[3][-1]):
+            for acc in self._pushed:
+                acc.pop()
+            raise ValueError("push: instrument, frame, note_id and record differ in length")
+
+    def schedule(self, out_len, max_spans):
+        """one buffer of out_len frames from what was pushed since the last call: enqueued, no sync"""
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs)) if xs else np.zeros(0, dt)
+        inst, frame, ids, rec = (cat(xs, dt) for xs, dt in zip(self._pushed, (np.uint32, np.uint32, np.uint64, self.record_dtype)))
+        self._pushed = ([], [], [], [])
+        batch = abi.BankImpulses(len(inst), inst.ctypes.data, frame.ctypes.data, ids.ctypes.data, rec.ctypes.data)
+        abi.check(self.lib.zh_voice_bank_schedule_live(self.handle, out_len, max_spans, C.byref(batch) if len(inst) else None),
+                  "zh_voice_bank_schedule_live")
+
+    def get_state(self):
+        """(next_event_id [n] uint64, per-voice zh_voice_bank_live_voice_state array)"""
+        next_id = np.zeros(max(self.n_instruments, 1), np.uint64)
+        voices = (abi.VoiceBankLiveVoiceState * max(self.n_voices, 1))()
+        abi.check(self.lib.zh_voice_bank_live_get_state(self.handle, next_id.ctypes.data_as(C.POINTER(C.c_uint64)), voices), "zh_voice_bank_live_get_state")
+        return next_id, voices
+
+    def set_state(self, state):
+        next_id = np.ascontiguousarray(state[0], np.uint64)
+        abi.check(self.lib.zh_voice_bank_live_set_state(self.handle, next_id.ctypes.data_as(C.POINTER(C.c_uint64)), state[1]), "zh_voice_bank_live_set_state")

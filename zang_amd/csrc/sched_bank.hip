@@ -17,7 +17,8 @@
 #include <vector>
 
 namespace {
-constexpr uint32_t kBankBlock = 256, kBankChunk = 32, kBankMaxIpb = 64, kBankLdsBytes = 60 * 1024, kBankDefaultRows = 4;
+constexpr uint32_t kBankBlock = 256, kBankChunk = 32, kBankMaxIpb = 64, kBankLdsBytes = 60 * 1024, kBankDefaultRows = 4,
+                   kBankStageSlots = 4;
 
 struct BankFrames { uint32_t n, base, first; uint32_t f[kBankChunk]; };   // by value: read when the call is made
 struct BankArgs {
@@ -101,6 +102,80 @@ __global__ void __launch_bounds__(kBankBlock) k_voice_bank_schedule(BankArgs a, 
         a.slot_flags[v0 + j] = s_flags[li]; a.slot_note[v0 + j] = s_note[li]; a.slot_event[v0 + j] = s_event[li];
     }
 }
+
+// The live half: a bank with no song takes one batch of pushed impulses per buffer (ImpulseQueue -> PolyphonyDispatcher ->
+// Trigger, examples/example_polyphony2.zig:61-95).  Same shape as above, one buffer per launch; the batch arrives sorted by
+// instrument in CSR form, and a Trigger's carried note is its record, kept per voice in `carried` ([word][voice]).
+struct LiveArgs {
+    ZsSong batch;                               // note_id / rec of this call's impulses (t unused)
+    const uint32_t *offsets, *frame;            // [n + 1], [impulses]
+    uint32_t n, P, ipb;
+    uint64_t *next_event_id;                    // [n]
+    uint32_t *slot_flags; uint64_t *slot_note, *slot_event;   // [n * P]
+    uint32_t *trig_has; uint64_t *trig_note;    // [n * P]
+    uint32_t *carried;                          // [words][n * P]
+    uint32_t *count, *start, *end, *words;
+    uint8_t *note_on, *changed;
+    size_t plane;
+    uint32_t max_spans;
+    uint32_t *overflow;
+};
+
+__global__ void __launch_bounds__(kBankBlock) k_voice_bank_schedule_live(LiveArgs a, uint32_t out_len) {
+    extern __shared__ uint64_t bank_lds[];
+    const uint32_t ipb = a.ipb, P = a.P, tid = threadIdx.x;
+    uint64_t *s_note = bank_lds;                                  // [P][ipb]
+    uint64_t *s_event = s_note + (size_t)P * ipb;                 // [P][ipb]
+    uint32_t *s_flags = (uint32_t *)(s_event + (size_t)P * ipb);  // [P][ipb]
+    uint32_t *l_slot = s_flags + (size_t)P * ipb;                 // [32][ipb]
+    uint32_t *l_frame = l_slot + kZsMaxImpulses * ipb;
+    uint32_t *l_ev = l_frame + kZsMaxImpulses * ipb;
+    uint32_t *l_n = l_ev + kZsMaxImpulses * ipb;                  // [ipb]
+    const uint32_t inst0 = blockIdx.x * ipb;
+    const uint32_t n_inst = min(ipb, a.n - inst0);
+    const uint32_t n_sub = n_inst * P;
+    const size_t nv = (size_t)a.n * P, v0 = (size_t)inst0 * P;
+
+    for (uint32_t j = tid; j < n_sub; j += kBankBlock) {
+        const uint32_t li = (j % P) * ipb + j / P;
+        s_flags[li] = a.slot_flags[v0 + j]; s_note[li] = a.slot_note[v0 + j]; s_event[li] = a.slot_event[v0 + j];
+    }
+    __syncthreads();
+    if (tid < n_inst) {                                                            // phase A
+        const ZsSlots sl{s_flags + tid, s_note + tid, s_event + tid, ipb, P};
+        const ZsList list{l_slot + tid, l_frame + tid, l_ev + tid, ipb};
+        uint64_t next_id = a.next_event_id[inst0 + tid];
+        l_n[tid] = zs_push_dispatch(a.batch, a.frame, a.offsets[inst0 + tid], a.offsets[inst0 + tid + 1], next_id, sl, list);
+        a.next_event_id[inst0 + tid] = next_id;
+    }
+    __syncthreads();
+    uint32_t dropped = 0;
+    for (uint32_t j = tid; j < n_sub; j += kBankBlock) {                           // phase B
+        const uint32_t i = j / P, slot = j % P;
+        const size_t v = v0 + j;
+        const ZsList list{l_slot + i, l_frame + i, l_ev + i, ipb};
+        const ZsCarried carried{a.carried + v, nv};
+        ZsTrigger tr{a.trig_has[v], kZsCarried, a.trig_note[v]};
+        uint32_t k = 0;
+        zs_trigger_buffer(tr, a.batch, list, l_n[i], slot, out_len, [&](uint32_t s, uint32_t e, uint32_t ev, uint32_t changed) {
+            if (k >= a.max_spans) { dropped++; return; }
+            const size_t idx = (size_t)k * nv + v;
+            a.start[idx] = s; a.end[idx] = e;
+            for (uint32_t w = 0; w < a.batch.words; w++) a.words[w * a.plane + idx] = zs_live_word(a.batch, carried, ev, w);
+            a.note_on[idx] = zs_live_note_on(a.batch, carried, ev) ? 1 : 0;
+            a.changed[idx] = (uint8_t)changed;
+            k++;
+        });
+        zs_live_keep(tr, a.batch, carried);
+        a.count[v] = k;
+        a.trig_has[v] = tr.has_note; a.trig_note[v] = tr.note_id;
+    }
+    if (dropped) atomicAdd(a.overflow, dropped);
+    for (uint32_t j = tid; j < n_sub; j += kBankBlock) {
+        const uint32_t li = (j % P) * ipb + j / P;
+        a.slot_flags[v0 + j] = s_flags[li]; a.slot_note[v0 + j] = s_note[li]; a.slot_event[v0 + j] = s_event[li];
+    }
+}
 }  // namespace
 
 struct zh_voice_bank {
@@ -112,9 +187,20 @@ struct zh_voice_bank {
     uint32_t *slot_flags, *trig_has, *trig_ev; uint64_t *slot_note, *slot_event, *trig_note;
     uint32_t *count, *start, *end, *wordsbuf; uint8_t *note_on, *changed;
     uint32_t *overflow;
+    // a live bank (zh_voice_bank_create_live): no song, no tracker; per call one batch of pushed impulses
+    bool live;
+    uint32_t max_impulses;
+    uint64_t *next_event_id;                      // [n] ImpulseQueue.next_event_id
+    uint32_t *carried;                            // [words][n * P] the Triggers' carried records
+    uint8_t *batch;                               // device copy of the call's sorted batch (bank_batch_bytes at most)
+    uint8_t *stage[kBankStageSlots];              // pinned host staging, a ring: slot k is free once stage_done[k] has passed
+    hipEvent_t stage_done[kBankStageSlots];
+    uint32_t stage_next;
 };
 
 namespace {
+// a batch of m impulses as ONE block: u64 note_id[m], u32 offsets[n + 1], u32 frame[m], u32 rec[m][words]
+size_t bank_batch_bytes(const zh_voice_bank *b, size_t m) { return m * 8 + ((size_t)b->n + 1) * 4 + m * 4 + m * 4 * b->words; }
 size_t bank_voices(const zh_voice_bank *b) { return (size_t)b->n * b->P; }
 void bank_free_tables(zh_voice_bank *b) {
     (void)hipFree(b->start); (void)hipFree(b->end); (void)hipFree(b->wordsbuf); (void)hipFree(b->note_on); (void)hipFree(b->changed);
@@ -125,6 +211,11 @@ void bank_free(zh_voice_bank *b) {
     (void)hipFree(b->t); (void)hipFree(b->note_id); (void)hipFree(b->rec); (void)hipFree(b->offsets); (void)hipFree(b->next); (void)hipFree(b->clock);
     (void)hipFree(b->slot_flags); (void)hipFree(b->trig_has); (void)hipFree(b->trig_ev); (void)hipFree(b->slot_note); (void)hipFree(b->slot_event);
     (void)hipFree(b->trig_note); (void)hipFree(b->count); (void)hipFree(b->overflow);
+    (void)hipFree(b->next_event_id); (void)hipFree(b->carried); (void)hipFree(b->batch);
+    for (uint32_t k = 0; k < kBankStageSlots; k++) {
+        if (b->stage[k]) (void)hipHostFree(b->stage[k]);
+        if (b->stage_done[k]) (void)hipEventDestroy(b->stage_done[k]);
+    }
 }
 int bank_alloc_tables(zh_voice_bank *b, uint32_t rows) {
     const size_t cells = (size_t)rows * bank_voices(b);
@@ -140,11 +231,13 @@ int bank_alloc_tables(zh_voice_bank *b, uint32_t rows) {
 int bank_clear_state(zh_voice_bank *b) {                          // example_song.zig:318-324 (and Trigger.init / NoteTracker.init)
     const size_t nv = bank_voices(b);
     hipStream_t st = b->ctx->stream;
-    if (b->n) { ZH_TRY(hipMemsetAsync(b->next, 0, (size_t)b->n * 4, st)); ZH_TRY(hipMemsetAsync(b->clock, 0, (size_t)b->n * 4, st)); }
+    // (a live bank has no tracker, and ImpulseQueue has no reset: next_event_id stays)
+    if (b->n && !b->live) { ZH_TRY(hipMemsetAsync(b->next, 0, (size_t)b->n * 4, st)); ZH_TRY(hipMemsetAsync(b->clock, 0, (size_t)b->n * 4, st)); }
     if (nv) {
         ZH_TRY(hipMemsetAsync(b->slot_flags, 0, nv * 4, st)); ZH_TRY(hipMemsetAsync(b->slot_note, 0, nv * 8, st));
         ZH_TRY(hipMemsetAsync(b->slot_event, 0, nv * 8, st)); ZH_TRY(hipMemsetAsync(b->trig_has, 0, nv * 4, st));
-        ZH_TRY(hipMemsetAsync(b->trig_ev, 0, nv * 4, st)); ZH_TRY(hipMemsetAsync(b->trig_note, 0, nv * 8, st));
+        ZH_TRY(hipMemsetAsync(b->trig_note, 0, nv * 8, st));
+        if (!b->live) ZH_TRY(hipMemsetAsync(b->trig_ev, 0, nv * 4, st));
     }
     return ZH_OK;
 }
@@ -235,7 +328,7 @@ int zh_voice_bank_reserve(zh_voice_bank *b, uint32_t max_rows) { ZH_GUARD(b ? b-
 
 int zh_voice_bank_schedule(zh_voice_bank *b, float sample_rate, const uint32_t *frames, uint32_t n_buffers, uint32_t max_spans) {
     ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || (n_buffers && !frames) || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
+    if (!b || b->live || (n_buffers && !frames) || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
     uint64_t total = 0;
     for (uint32_t i = 0; i < n_buffers; i++) total += frames[i];
     if (total >> 32) return ZH_ERR_INVALID;
@@ -292,7 +385,7 @@ int zh_voice_bank_overflows(zh_voice_bank *b, uint64_t *out) { ZH_GUARD(b ? b->c
 
 int zh_voice_bank_get_state(zh_voice_bank *b, zh_voice_bank_instrument_state *instruments, zh_voice_bank_voice_state *voices) {
     ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || (b->n && (!instruments || !voices))) return ZH_ERR_INVALID;
+    if (!b || b->live || (b->n && (!instruments || !voices))) return ZH_ERR_INVALID;
     const size_t nv = bank_voices(b);
     std::vector<uint32_t> next, sf, th, te;
     std::vector<float> clock;
@@ -314,7 +407,7 @@ int zh_voice_bank_get_state(zh_voice_bank *b, zh_voice_bank_instrument_state *in
 
 int zh_voice_bank_set_state(zh_voice_bank *b, const zh_voice_bank_instrument_state *instruments, const zh_voice_bank_voice_state *voices) {
     ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || (b->n && (!instruments || !voices))) return ZH_ERR_INVALID;
+    if (!b || b->live || (b->n && (!instruments || !voices))) return ZH_ERR_INVALID;
     if (b->ctx->capturing) return ZH_ERR_UNSUPPORTED;
     const size_t nv = bank_voices(b);
     if (!nv) return ZH_OK;
@@ -339,6 +432,145 @@ int zh_voice_bank_set_state(zh_voice_bank *b, const zh_voice_bank_instrument_sta
     if (!rc) rc = zh_upload(b->ctx, b->trig_has, th.data(), nv * 4);
     if (!rc) rc = zh_upload(b->ctx, b->trig_ev, te.data(), nv * 4);
     if (!rc) rc = zh_upload(b->ctx, b->trig_note, tn.data(), nv * 8);
+    return rc;
+}
+
+int zh_voice_bank_create_live(zh_ctx *ctx, uint32_t n_instruments, uint32_t polyphony, uint32_t params_size, uint32_t note_on_offset,
+                              uint32_t max_impulses_per_call, zh_voice_bank **out) {
+    ZH_GUARD(ctx);
+    if (!ctx || !out || polyphony == 0 || params_size == 0 || params_size > ZH_MAX_PARAMS_SIZE || (params_size & 3u) ||
+        note_on_offset >= params_size || max_impulses_per_call == kZsCarried)
+        return ZH_ERR_INVALID;
+    *out = nullptr;
+    if (ctx->capturing) return ZH_ERR_UNSUPPORTED;
+    if ((uint64_t)n_instruments * polyphony > (1ull << 31)) return ZH_ERR_INVALID;
+    uint32_t ipb = kBankMaxIpb;
+    while (ipb > 1 && bank_lds_bytes(ipb, polyphony) > kBankLdsBytes) ipb /= 2;
+    if (bank_lds_bytes(ipb, polyphony) > kBankLdsBytes) return ZH_ERR_INVALID;
+    zh_voice_bank *b = new (std::nothrow) zh_voice_bank();
+    if (!b) return ZH_ERR_INVALID;
+    memset(b, 0, sizeof *b);
+    b->ctx = ctx; b->n = n_instruments; b->P = polyphony; b->words = params_size / 4; b->note_on_offset = note_on_offset; b->ipb = ipb;
+    b->live = true; b->max_impulses = max_impulses_per_call;
+    const size_t nv = bank_voices(b), bytes = bank_batch_bytes(b, max_impulses_per_call);
+    int rc = dev_alloc(&b->next_event_id, n_instruments);
+    if (!rc) rc = dev_alloc(&b->slot_flags, nv);
+    if (!rc) rc = dev_alloc(&b->slot_note, nv);
+    if (!rc) rc = dev_alloc(&b->slot_event, nv);
+    if (!rc) rc = dev_alloc(&b->trig_has, nv);
+    if (!rc) rc = dev_alloc(&b->trig_note, nv);
+    if (!rc) rc = dev_alloc(&b->carried, nv * b->words);
+    if (!rc) rc = dev_alloc(&b->count, nv);
+    if (!rc) rc = dev_alloc(&b->overflow, 1);
+    if (!rc && n_instruments) rc = dev_alloc(&b->batch, bytes);
+    for (uint32_t k = 0; !rc && n_instruments && k < kBankStageSlots; k++) {
+        rc = (int)hipHostMalloc((void **)&b->stage[k], bytes, hipHostMallocDefault);
+        if (!rc) rc = (int)hipEventCreateWithFlags(&b->stage_done[k], hipEventDisableTiming);
+    }
+    if (!rc) rc = bank_alloc_tables(b, kBankDefaultRows);
+    if (!rc) rc = (int)hipMemsetAsync(b->overflow, 0, 4, ctx->stream);
+    if (!rc && nv) rc = (int)hipMemsetAsync(b->count, 0, nv * 4, ctx->stream);
+    if (!rc && nv) rc = (int)hipMemsetAsync(b->carried, 0, nv * b->words * 4, ctx->stream);
+    if (!rc) rc = bank_clear_state(b);
+    if (!rc && n_instruments) {                                                    // ImpulseQueue.init: next_event_id = 1
+        const std::vector<uint64_t> ones(n_instruments, 1);
+        rc = zh_upload(ctx, b->next_event_id, ones.data(), (size_t)n_instruments * 8);
+    }
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); bank_free(b); delete b; (void)hipGetLastError(); return rc; }
+    *out = b;
+    return ZH_OK;
+}
+
+int zh_voice_bank_schedule_live(zh_voice_bank *b, uint32_t out_len, uint32_t max_spans, const zh_bank_impulses *batch) {
+    ZH_GUARD(b ? b->ctx : nullptr);
+    if (!b || !b->live || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
+    const uint32_t m = batch ? batch->n : 0u;
+    if (m > b->max_impulses || (m && (!batch->instrument || !batch->frame || !batch->note_id || !batch->paramses))) return ZH_ERR_INVALID;
+    for (uint32_t i = 0; i < m; i++) if (batch->instrument[i] >= b->n) return ZH_ERR_INVALID;
+    if (b->ctx->capturing) return ZH_ERR_UNSUPPORTED;             // (a replay would read host memory that has since changed)
+    if (b->n == 0) return ZH_OK;
+    hipStream_t st = b->ctx->stream;
+    // the batch, sorted by instrument (a stable counting sort into CSR), in a staging slot whose last copy has completed
+    const uint32_t slot = b->stage_next;
+    b->stage_next = (slot + 1) % kBankStageSlots;
+    ZH_TRY(hipEventSynchronize(b->stage_done[slot]));
+    uint8_t *h = b->stage[slot];
+    uint64_t *h_note = (uint64_t *)h;
+    uint32_t *h_off = (uint32_t *)(h + (size_t)m * 8), *h_frame = h_off + b->n + 1, *h_rec = h_frame + m;
+    memset(h_off, 0, ((size_t)b->n + 1) * 4);
+    for (uint32_t i = 0; i < m; i++) h_off[batch->instrument[i] + 1] += 1;
+    for (uint32_t i = 0; i < b->n; i++) h_off[i + 1] += h_off[i];
+    const size_t psize = (size_t)b->words * 4;
+    for (uint32_t i = 0; i < m; i++) {                            // h_off[k] = the next free place of instrument k ...
+        const uint32_t at = h_off[batch->instrument[i]]++;
+        h_note[at] = batch->note_id[i]; h_frame[at] = batch->frame[i];
+        memcpy(h_rec + (size_t)at * b->words, (const uint8_t *)batch->paramses + i * psize, psize);
+    }
+    for (uint32_t i = b->n; i > 0; i--) h_off[i] = h_off[i - 1];  // ... = the begin of k + 1 once all are placed: shift back
+    h_off[0] = 0;
+    ZH_TRY(hipMemcpyAsync(b->batch, h, bank_batch_bytes(b, m), hipMemcpyHostToDevice, st));
+    ZH_TRY(hipEventRecord(b->stage_done[slot], st));
+    LiveArgs a;
+    uint8_t *d = b->batch;
+    a.batch = ZsSong{nullptr, (const uint64_t *)d, (const uint32_t *)(d + (size_t)m * 8) + b->n + 1 + m, b->words, b->note_on_offset / 4,
+                     (b->note_on_offset & 3u) * 8};
+    a.offsets = (const uint32_t *)(d + (size_t)m * 8); a.frame = a.offsets + b->n + 1;
+    a.n = b->n; a.P = b->P; a.ipb = b->ipb;
+    a.next_event_id = b->next_event_id;
+    a.slot_flags = b->slot_flags; a.slot_note = b->slot_note; a.slot_event = b->slot_event;
+    a.trig_has = b->trig_has; a.trig_note = b->trig_note; a.carried = b->carried;
+    a.count = b->count; a.start = b->start; a.end = b->end; a.words = b->wordsbuf; a.note_on = b->note_on; a.changed = b->changed;
+    a.plane = (size_t)b->rows * bank_voices(b); a.max_spans = max_spans; a.overflow = b->overflow;
+    ZH_LAUNCH(k_voice_bank_schedule_live, dim3((b->n + b->ipb - 1) / b->ipb), dim3(kBankBlock), bank_lds_bytes(b->ipb, b->P), st, a, out_len);
+    return zh_launch_status();
+}
+
+int zh_voice_bank_live_get_state(zh_voice_bank *b, uint64_t *next_event_id, zh_voice_bank_live_voice_state *voices) {
+    ZH_GUARD(b ? b->ctx : nullptr);
+    if (!b || !b->live || (b->n && (!next_event_id || !voices))) return ZH_ERR_INVALID;
+    const size_t nv = bank_voices(b);
+    std::vector<uint32_t> sf, th, cw;
+    std::vector<uint64_t> sn, se, tn;
+    int rc = b->n ? zh_download(b->ctx, next_event_id, b->next_event_id, (size_t)b->n * 8) : ZH_OK;
+    if (!rc) rc = bank_down(b, sf, b->slot_flags, nv);
+    if (!rc) rc = bank_down(b, sn, b->slot_note, nv);
+    if (!rc) rc = bank_down(b, se, b->slot_event, nv);
+    if (!rc) rc = bank_down(b, th, b->trig_has, nv);
+    if (!rc) rc = bank_down(b, tn, b->trig_note, nv);
+    if (!rc) rc = bank_down(b, cw, b->carried, nv * b->words);
+    if (rc) return rc;
+    for (size_t v = 0; v < nv; v++) {
+        zh_voice_bank_live_voice_state s;
+        memset(&s, 0, sizeof s);
+        s.used = (sf[v] & ZS_SLOT_USED) ? 1u : 0u; s.note_on = (sf[v] & ZS_SLOT_ON) ? 1u : 0u; s.note_id = sn[v]; s.event_id = se[v];
+        s.has_note = th[v] ? 1u : 0u; s.trigger_note_id = tn[v];
+        if (s.has_note) for (uint32_t w = 0; w < b->words; w++) s.carried[w] = cw[w * nv + v];
+        voices[v] = s;
+    }
+    return ZH_OK;
+}
+
+int zh_voice_bank_live_set_state(zh_voice_bank *b, const uint64_t *next_event_id, const zh_voice_bank_live_voice_state *voices) {
+    ZH_GUARD(b ? b->ctx : nullptr);
+    if (!b || !b->live || (b->n && (!next_event_id || !voices))) return ZH_ERR_INVALID;
+    if (b->ctx->capturing) return ZH_ERR_UNSUPPORTED;
+    const size_t nv = bank_voices(b);
+    if (!nv) return ZH_OK;
+    std::vector<uint32_t> sf(nv), th(nv), cw(nv * b->words);
+    std::vector<uint64_t> sn(nv), se(nv), tn(nv);
+    for (size_t v = 0; v < nv; v++) {
+        sf[v] = (voices[v].used ? ZS_SLOT_USED : 0u) | (voices[v].note_on ? ZS_SLOT_ON : 0u);
+        sn[v] = voices[v].note_id; se[v] = voices[v].event_id;
+        th[v] = voices[v].has_note ? 1u : 0u; tn[v] = voices[v].trigger_note_id;
+        for (uint32_t w = 0; w < b->words; w++) cw[w * nv + v] = voices[v].carried[w];
+    }
+    int rc = zh_upload(b->ctx, b->next_event_id, next_event_id, (size_t)b->n * 8);
+    if (!rc) rc = zh_upload(b->ctx, b->slot_flags, sf.data(), nv * 4);
+    if (!rc) rc = zh_upload(b->ctx, b->slot_note, sn.data(), nv * 8);
+    if (!rc) rc = zh_upload(b->ctx, b->slot_event, se.data(), nv * 8);
+    if (!rc) rc = zh_upload(b->ctx, b->trig_has, th.data(), nv * 4);
+    if (!rc) rc = zh_upload(b->ctx, b->trig_note, tn.data(), nv * 8);
+    if (!rc) rc = zh_upload(b->ctx, b->carried, cw.data(), nv * b->words * 4);
     return rc;
 }
 

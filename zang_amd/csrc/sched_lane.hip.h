@@ -161,3 +161,46 @@ ZS_HD void zs_trigger_buffer(ZsTrigger &tr, const ZsSong &song, const ZsList &li
         start = s_end;
     }
 }
+
+// ---- live banks (k_voice_bank_schedule_live): the events of a buffer are pushed from outside (ImpulseQueue, notes.zig:72-128)
+// One call's batch, sorted by instrument into CSR, is viewed through ZsSong (`t` unused): an impulse's `ev` is its index in the
+// batch, and zs_dispatch_one / zs_trigger_buffer run on it unchanged.  The batch is gone by the next buffer, so a Trigger's carried
+// note is not an index but the record itself: per-voice words, at most kZsMaxWords of them, and `ev` == kZsCarried names them.
+// Between buffers every Trigger's `ev` is kZsCarried (zs_live_keep); a batch holds fewer than 2^32 - 1 impulses.
+constexpr uint32_t kZsCarried = 0xffffffffu;
+constexpr uint32_t kZsMaxWords = 16;        // ZH_MAX_PARAMS_SIZE / 4
+struct ZsCarried {
+    uint32_t *words;           // word w of ONE voice's carried record at index w * stride
+    size_t stride;
+};
+
+// ImpulseQueue.push for the impulses [begin, end) of one instrument in push order, then consume, each accepted impulse handed
+// straight to the dispatcher.  A push is dropped when 32 are accepted (:108-111) or when its frame is below the last accepted
+// one's (:112-118); an accepted one takes event_id = next_event_id++ (:119-126).  Returns the number of list entries.
+ZS_HD uint32_t zs_push_dispatch(const ZsSong &batch, const uint32_t *frame, uint32_t begin, uint32_t end, uint64_t &next_event_id,
+                                const ZsSlots &sl, const ZsList &list) {
+    uint32_t accepted = 0, listed = 0, last = 0;
+    for (uint32_t ev = begin; ev < end && accepted < kZsMaxImpulses; ev++) {
+        const uint32_t f = frame[ev];
+        if (accepted > 0 && f < last) continue;
+        last = f; accepted += 1;
+        const uint64_t event_id = next_event_id;
+        next_event_id += 1;
+        listed = zs_dispatch_one(sl, list, listed, f, ev, batch.note_id[ev], zs_note_on(batch, ev), event_id);
+    }
+    return listed;
+}
+
+// word w of the record a sub-span's paint takes: the carried record's, or the batch's
+ZS_HD uint32_t zs_live_word(const ZsSong &batch, const ZsCarried &c, uint32_t ev, uint32_t w) {
+    return ev == kZsCarried ? c.words[w * c.stride] : batch.rec[(size_t)ev * batch.words + w];
+}
+ZS_HD bool zs_live_note_on(const ZsSong &batch, const ZsCarried &c, uint32_t ev) {
+    return ((zs_live_word(batch, c, ev, batch.on_word) >> batch.on_shift) & 0xffu) != 0;
+}
+// after a voice's Trigger loop: the record of the note it ends on moves from the batch into the voice's carried words
+ZS_HD void zs_live_keep(ZsTrigger &tr, const ZsSong &batch, const ZsCarried &c) {
+    if (!tr.has_note || tr.ev == kZsCarried) return;
+    for (uint32_t w = 0; w < batch.words; w++) c.words[w * c.stride] = batch.rec[(size_t)tr.ev * batch.words + w];
+    tr.ev = kZsCarried;
+}
