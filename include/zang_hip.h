@@ -711,6 +711,48 @@ ZH_API int zh_pmosc_paint(zh_pmosc *m, uint32_t span_start, uint32_t span_end, c
 ZH_API int zh_pmosc_paint_spans(zh_pmosc *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
                                 const zh_buf *temps, float sample_rate, const zh_span_table *table, uint32_t flags);
 
+/* ---------------------------------------------------------------- FM synth voice (examples/example_fmsynth.zig:22-356)
+ * The OPL-style two-operator instrument as ONE kernel: Instrument (:244-356) = modulator + carrier Operator (:92-242), each an
+ * Oscillator (:26-89: four waveforms, its own last two samples fed back into its phase) times volume, tremolo and an Envelope
+ * with cubed curves.  Algorithm 0 adds both operators into the output, modulator first; algorithm 1 makes the modulator the
+ * carrier's phase.  Bit-identical to the reference's stage-by-stage composition.
+ * `group` consecutive voices form one INSTRUMENT (a synth's polyphony): instrument j = voice / group selects the patch and the
+ * column of the two LFO images, which hold one column per instrument ([frame][ceil(n_voices / group)]) and are read at the
+ * absolute frame.  A patch is the 22 discrete parameters of :375-398; zh_fm_set_patches turns them into gains and envelope times
+ * once (:135-203), on the device, and a paint only loads its instrument's numbers.  Waveform, algorithm and feedback are
+ * per voice at run time: voices with different patches share a launch.
+ * ZH_FM_SPLIT_OPERATORS (these two paints only): outputs[0] has 2 * n_voices columns; column 2v receives what voice v's modulator
+ * adds to the output (nothing in algorithm 1), column 2v + 1 what its carrier adds.  The reference's synth adds every voice into
+ * ONE buffer, (acc + m_v) + c_v (:462, :302, :335), which in f32 is not acc + (m_v + c_v): zh_mixdown_groups over groups of
+ * 2 * group columns of the split image reproduces that order.  Without the flag a voice's column is its own paint, (out + m) + c.
+ * ZH_ERR_INVALID: NULL or mis-sized images (outputs[0]: n_voices or 2 * n_voices columns; the LFO images: one per instrument), a
+ * span outside an image, group == 0, a bad table, a patch value outside its num_values (nothing changes then), n_patches neither
+ * 1 nor the number of instruments.  ZH_ERR_UNSUPPORTED: ZH_PAINT_TOLERANT (exact forms only); zh_fm_set_patches while a capture
+ * records (it copies from the host).  Both paints are capturable; neither allocates nor synchronises. */
+enum { ZH_FM_MOD_FREQ_MUL = 0, ZH_FM_MOD_WAVEFORM = 1, ZH_FM_MOD_VOLUME = 2, ZH_FM_MOD_ATTACK = 3, ZH_FM_MOD_DECAY = 4,
+       ZH_FM_MOD_SUSTAIN = 5, ZH_FM_MOD_RELEASE = 6, ZH_FM_MOD_TREMOLO = 7, ZH_FM_MOD_VIBRATO = 8, ZH_FM_MOD_FEEDBACK = 9,
+       ZH_FM_CAR_FREQ_MUL = 10, ZH_FM_CAR_WAVEFORM = 11, ZH_FM_CAR_VOLUME = 12, ZH_FM_CAR_ATTACK = 13, ZH_FM_CAR_DECAY = 14,
+       ZH_FM_CAR_SUSTAIN = 15, ZH_FM_CAR_RELEASE = 16, ZH_FM_CAR_TREMOLO = 17, ZH_FM_CAR_VIBRATO = 18, ZH_FM_TREMOLO_DEPTH = 19,
+       ZH_FM_VIBRATO_DEPTH = 20, ZH_FM_ALGORITHM = 21, ZH_FM_PATCH_VALUES = 22 };   /* the order of parameters[0..21], :375-398 */
+enum { ZH_FM_SPLIT_OPERATORS = 16 };   /* a paint flag beside ZH_PAINT_*: zh_fm_paint and zh_fm_paint_spans only */
+typedef struct zh_fm zh_fm;
+typedef struct zh_fm_patch { uint32_t value[22]; } zh_fm_patch;                /* [ZH_FM_PATCH_VALUES]: current_value, :376-397 */
+typedef struct zh_fm_params { float sample_rate; uint32_t reserved; zh_buf tremolo_input, vibrato_input; zh_f32 freq; zh_bool note_on; } zh_fm_params; /* :247-275 */
+typedef struct zh_fm_op_state { float t, feedback1, feedback2; uint32_t reserved; zh_envelope_state env; } zh_fm_op_state;   /* :37-39, :116-117 */
+typedef struct zh_fm_state { zh_fm_op_state modulator, carrier; } zh_fm_state;                         /* :277-278 */
+ZH_API int zh_fm_patch_default(zh_fm_patch *patch);                                                    /* the current_values of :376-397 */
+ZH_API int zh_fm_create(zh_ctx *ctx, uint32_t n_voices, uint32_t group, zh_fm **out);                  /* init() :280-285, default patch */
+ZH_API int zh_fm_destroy(zh_fm *m);
+ZH_API int zh_fm_set_patches(zh_fm *m, const zh_fm_patch *patches, uint32_t n_patches);                /* :135-203, once instead of per paint */
+ZH_API int zh_fm_get_state(zh_fm *m, zh_fm_state *host);
+ZH_API int zh_fm_set_state(zh_fm *m, const zh_fm_state *host);
+ZH_API int zh_fm_paint(zh_fm *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
+                       const zh_buf *temps /*[3], unused; may be NULL*/,
+                       zh_bool note_id_changed, const zh_fm_params *params, uint32_t flags);           /* :287-355 */
+ZH_API int zh_fm_paint_spans(zh_fm *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
+                             const zh_buf *temps, float sample_rate, zh_buf tremolo_input, zh_buf vibrato_input,
+                             const zh_span_table *table, uint32_t flags);                               /* the Trigger loop :457-496; freq / note_on = NoteParams :365-368 */
+
 /* ---------------------------------------------------------------- zangscript modules
  * The reference compiles its module DSL to Zig source (tools/zangc.zig -> src/zangscript/codegen_zig.zig) that is
  * then built into the host program.  Here the same front-end (python -m zang_amd.zangc, zang_amd/zangscript/)

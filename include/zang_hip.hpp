@@ -294,6 +294,50 @@ private:
     }
 };
 
+// The FM synth voice of examples/example_fmsynth.zig (:22-356) for n_voices voices, `group` consecutive ones per instrument (a synth's
+// polyphony: one patch and one column of the LFO images each).  paint / paintSpans as on the fused composites below; flags may
+// carry ZH_FM_SPLIT_OPERATORS (outputs[0] then has 2 * n_voices columns: the modulator's and the carrier's part of every voice).
+class FMInstrument {
+    zh_fm *h_ = nullptr;
+    uint32_t n_, group_;
+
+public:
+    static constexpr size_t num_outputs = 1;
+    static constexpr size_t num_temps = 3;
+    using Params = zh_fm_params;
+    using Patch = zh_fm_patch;
+    FMInstrument(Context &ctx, uint32_t n_voices, uint32_t group = 1) : n_(n_voices), group_(group) {
+        check(zh_fm_create(ctx.get(), n_voices, group, &h_), "zh_fm_create");
+    }
+    ~FMInstrument() { if (h_) zh_fm_destroy(h_); }
+    FMInstrument(const FMInstrument &) = delete;
+    FMInstrument &operator=(const FMInstrument &) = delete;
+    zh_fm *get() const { return h_; }
+    uint32_t voices() const { return n_; }
+    uint32_t instruments() const { return group_ ? (n_ + group_ - 1) / group_ : 0; }
+    static Patch defaultPatch() { Patch p{}; check(zh_fm_patch_default(&p), "zh_fm_patch_default"); return p; }   // :376-397
+    // one patch for every instrument, or one per instrument; a value outside its num_values is refused and nothing changes
+    void setPatches(const std::vector<Patch> &patches) { check(zh_fm_set_patches(h_, patches.data(), (uint32_t)patches.size()), "zh_fm_set_patches"); }
+    std::vector<zh_fm_state> getState() {
+        std::vector<zh_fm_state> s(n_);
+        check(zh_fm_get_state(h_, s.data()), "zh_fm_get_state");
+        return s;
+    }
+    void setState(const std::vector<zh_fm_state> &s) {
+        if (s.size() != n_) throw Error(ZH_ERR_INVALID, "FMInstrument::setState: a state of another instrument");
+        check(zh_fm_set_state(h_, s.data()), "zh_fm_set_state");
+    }
+    void paint(Span span, const std::array<zh_buf, 1> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_fm_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_fm_paint");
+    }
+    // the synth's Trigger loop (:457-496) for every voice in one call; `table`: uploaded by the host, or a voice bank's spanTable()
+    void paintSpans(Span span, const std::array<zh_buf, 1> &outputs, float sample_rate, const zh_buf &tremolo_input, const zh_buf &vibrato_input,
+                    const zh_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_fm_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, sample_rate, tremolo_input, vibrato_input, &table, flags),
+              "zh_fm_paint_spans");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -62,7 +62,9 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 *[("zh_%s_paint_spans" % m, "span_params") for m in ("sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
                                                                      "filter", "sampler", "decimator", "distortion")],
                 # the batch call reads n_buffers elements of each
-                ("zh_nice_paint_mix_stereo_batch", "note_id_changed"), ("zh_nice_paint_mix_stereo_batch", "params")}
+                ("zh_nice_paint_mix_stereo_batch", "note_id_changed"), ("zh_nice_paint_mix_stereo_batch", "params"),
+                # n_patches elements
+                ("zh_fm_set_patches", "patches")}
 # scalar pointer parameters that are a single out value, not an array
 ONE_SCALAR = {"ms", "state_words", "noise_fields", "n_params", "num_temps", "code_size_out", "default_value", "current_value"}
 

@@ -17,6 +17,12 @@ COMM_ID_BYTES = 128
 PAINT_ADD, PAINT_ZERO_FIRST = 0, 1
 PAINT_PARAMS_UNCHANGED = 4
 PAINT_TOLERANT = 8
+FM_SPLIT_OPERATORS = 16
+FM_PATCH_VALUES = 22
+# the order of parameters[0..21] (examples/example_fmsynth.zig:375-398)
+(FM_MOD_FREQ_MUL, FM_MOD_WAVEFORM, FM_MOD_VOLUME, FM_MOD_ATTACK, FM_MOD_DECAY, FM_MOD_SUSTAIN, FM_MOD_RELEASE, FM_MOD_TREMOLO,
+ FM_MOD_VIBRATO, FM_MOD_FEEDBACK, FM_CAR_FREQ_MUL, FM_CAR_WAVEFORM, FM_CAR_VOLUME, FM_CAR_ATTACK, FM_CAR_DECAY, FM_CAR_SUSTAIN,
+ FM_CAR_RELEASE, FM_CAR_TREMOLO, FM_CAR_VIBRATO, FM_TREMOLO_DEPTH, FM_VIBRATO_DEPTH, FM_ALGORITHM) = range(22)
 ZH_CAPTURE_COALESCE = 1
 MIX_SEQUENTIAL = 2
 AUDIO_SIGNED8, AUDIO_SIGNED16_LSB = 0, 1
@@ -219,6 +225,22 @@ PMOscParams = NiceParams
 
 class PMOscState(C.Structure):
     _fields_ = [("carrier", SineOscState), ("modulator", SineOscState), ("env", EnvelopeState)]
+
+
+class FMPatch(C.Structure):
+    _fields_ = [("value", u32 * FM_PATCH_VALUES)]
+
+
+class FMParams(C.Structure):
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("tremolo_input", Buf), ("vibrato_input", Buf), ("freq", F32), ("note_on", Bool)]
+
+
+class FMOpState(C.Structure):
+    _fields_ = [("t", f32), ("feedback1", f32), ("feedback2", f32), ("reserved", u32), ("env", EnvelopeState)]
+
+
+class FMState(C.Structure):
+    _fields_ = [("modulator", FMOpState), ("carrier", FMOpState)]
 
 
 class SpanTable(C.Structure):
@@ -513,6 +535,14 @@ SIGNATURES = {
     "zh_pmosc_get_state": (C.c_int, [vp, vp]),
     "zh_pmosc_set_state": (C.c_int, [vp, vp]),
     "zh_pmosc_paint": (C.c_int, _paint(PMOscParams)),
+    "zh_fm_patch_default": (C.c_int, [P(FMPatch)]),
+    "zh_fm_create": (C.c_int, [vp, u32, u32, P(vp)]),
+    "zh_fm_destroy": (C.c_int, [vp]),
+    "zh_fm_set_patches": (C.c_int, [vp, vp, u32]),
+    "zh_fm_get_state": (C.c_int, [vp, vp]),
+    "zh_fm_set_state": (C.c_int, [vp, vp]),
+    "zh_fm_paint": (C.c_int, _paint(FMParams)),
+    "zh_fm_paint_spans": (C.c_int, [vp, u32, u32, P(Buf), P(Buf), f32, Buf, Buf, P(SpanTable), u32]),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

@@ -72,6 +72,51 @@ __device__ __forceinline__ void span_walk(const TB &tb, uint32_t V, uint32_t v, 
     advance(buf_end);          // a sub-span that ends with the buffer; empty sub-spans at buf_end
 }
 
+// span_walk for a kernel that brings its own frame loop (fm.hip.h: per-instrument input columns, two output columns): the same
+// walk, with every segment handed over as a whole.
+//   segment(i, seg_end, active): frames [i, seg_end) -- no lane of the wave starts or ends a sub-span inside; `active` = this lane
+//   is inside a sub-span there.  Called in live lanes only.
+template <class TB, class Begin, class Segment, class End>
+__device__ __forceinline__ void span_walk_segments(const TB &tb, uint32_t V, uint32_t v, bool live, uint32_t buf_start, uint32_t buf_end,
+                                                   Begin &&begin, Segment &&segment, End &&end_fn) {
+    const uint32_t cnt = live ? min(tb.count[v], tb.K) : 0;
+    uint32_t k = 0, cur_end = 0;
+    uint32_t next_start = cnt > 0 ? tb.start[v] : 0xffffffffu;
+    bool active = false;
+    auto advance = [&](uint32_t i) ZH_INLINE_LAMBDA {
+        for (;;) {
+            if (active) {
+                if (i == cur_end) {
+                    end_fn(); active = false; k++;
+                    next_start = k < cnt ? tb.start[(size_t)k * V + v] : 0xffffffffu;
+                    continue;
+                }
+                break;
+            }
+            if (i == next_start) {
+                const size_t idx = (size_t)k * V + v;
+                cur_end = tb.end[idx];
+                begin(idx, tb.nic[idx] != 0);
+                active = true;
+                continue;
+            }
+            break;
+        }
+    };
+    uint32_t i = buf_start;
+    while (i < buf_end) {
+        advance(i);
+        uint32_t ev = active ? cur_end : next_start;
+        ev = (ev > i && ev < buf_end) ? ev : buf_end;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ev = min(ev, (uint32_t)__shfl_xor((int)ev, off));
+        const uint32_t seg_end = __builtin_amdgcn_readfirstlane(ev);
+        if (live) segment(i, seg_end, active);
+        i = seg_end;
+    }
+    advance(buf_end);
+}
+
 // One builtin module's span paint, one lane per voice (kSeqBlock-lane blocks over seq_grid(V)).  The adapter A wraps the
 // module's lane object (voices.hip.h):
 //   A::Args                          the kernel's argument block (a.V = voices); the per-sub-span arrays ride in it

@@ -677,3 +677,63 @@ class PMOscInstrument(_Module):
         rc = self.lib.zh_pmosc_paint_spans(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps),
                                            float(sample_rate), C.byref(table.c), abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
         abi.check(rc, "zh_pmosc_paint_spans")
+
+
+class FMInstrument(_Module):
+    """examples/example_fmsynth.zig:22-356: the OPL-style two-operator FM Instrument (modulator + carrier Operator, each an
+    Oscillator with feedback and four waveforms times volume, tremolo and a cubed Envelope) as one fused kernel.
+    `group` consecutive voices form one instrument (a synth's polyphony): instrument v // group selects the patch and the
+    column of the two LFO images ([frame][n_instruments])."""
+    _prefix = "fm"
+    _state_ctype = abi.FMState
+    num_temps = 3
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        tremolo_input: Any
+        vibrato_input: Any
+        freq: Any
+        note_on: Any
+
+    def __init__(self, n_voices, ctx=None, group=1):
+        self.group = int(group)
+        super().__init__(n_voices, ctx, C.c_uint32(self.group))
+        self.n_instruments = -(-self.n_voices // self.group)
+
+    @classmethod
+    def init(cls, n_voices, ctx=None, group=1):
+        return cls(n_voices, ctx, group)
+
+    @staticmethod
+    def default_patch():
+        """the current_values of parameters[0..21] (:376-397), indexed by abi.FM_*"""
+        p = abi.FMPatch()
+        abi.check(abi.load().zh_fm_patch_default(C.byref(p)), "zh_fm_patch_default")
+        return list(p.value)
+
+    def set_patches(self, patches):
+        """`patches`: one list of 22 values (every instrument) or one per instrument.  A value outside its num_values is
+        refused and nothing changes."""
+        patches = np.ascontiguousarray(patches, dtype=np.uint32)
+        if patches.ndim == 1:
+            patches = patches[None, :]
+        assert patches.ndim == 2 and patches.shape[1] == abi.FM_PATCH_VALUES, patches.shape
+        abi.check(self.lib.zh_fm_set_patches(self.handle, patches.ctypes.data, patches.shape[0]), "zh_fm_set_patches")
+
+    @staticmethod
+    def _flags(zero_first, split):
+        return (abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD) | (abi.FM_SPLIT_OPERATORS if split else 0)
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False, split=False):
+        """split=True (ZH_FM_SPLIT_OPERATORS): outputs[0] has 2 * n_voices columns -- 2v: what the modulator adds to the
+        output (nothing in algorithm 1), 2v + 1: what the carrier adds."""
+        cp = abi.FMParams(params.sample_rate, 0, as_buf(params.tremolo_input), as_buf(params.vibrato_input), as_f32(params.freq),
+                          as_bool(params.note_on))
+        self._paint(span, outputs, temps, note_id_changed, cp, zero_first, abi.FM_SPLIT_OPERATORS if split else 0)
+
+    def paint_spans(self, span, outputs, temps, sample_rate, tremolo_input, vibrato_input, table, zero_first=False, split=False):
+        """The synth's Trigger loop (:457-496) for every voice in one launch (zang_amd.spans.SpanTable, or a voice bank's)."""
+        rc = self.lib.zh_fm_paint_spans(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps), float(sample_rate),
+                                        as_buf(tremolo_input), as_buf(vibrato_input), C.byref(table.c), self._flags(zero_first, split))
+        abi.check(rc, "zh_fm_paint_spans")
