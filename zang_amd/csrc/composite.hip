@@ -721,19 +721,11 @@ __global__ void __launch_bounds__(64) k_pmosc_ranges(PMOscArgs a, uint32_t *__re
     next[4 * V + v] = __builtin_bit_cast(uint32_t, n.env.last_value); next[5 * V + v] = __builtin_bit_cast(uint32_t, n.env.start);
 }
 // ------------------------------------------------------------------ span-table paints
-// One launch = for every voice, the reference's Trigger loop over its sub-spans
-// (examples/example_song.zig:336-347): begin() at a sub-span's first frame, end() after its last,
-// nothing painted between sub-spans.
-struct SpanTableP {
-    uint32_t K;
-    const uint32_t *count, *start, *end;
-    const float *freq;
-    const uint8_t *note_on, *nic;
-};
-
-// The walk is span_walk's (span_walk.hip.h): segments between the sub-span boundaries of a wave's lanes.
+// One launch = for every voice, the reference's Trigger loop over its sub-spans (examples/example_song.zig:336-347).  The walks
+// and their contract are span_walk.hip.h's: span_walk (a lane per voice: segments between the sub-span boundaries of a wave's
+// lanes) and span_walk_wave (a wave per voice).
 template <bool ZF>
-__global__ void __launch_bounds__(kSeqBlock) k_nice_spans(NiceArgs a, SpanTableP tb, Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(kSeqBlock) k_nice_spans(NiceArgs a, NoteSpanTableP tb, Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
     const bool live = v0 < a.V;
     const uint32_t v = live ? v0 : 0;                           // idle lanes shadow voice 0 read-only and store nothing
@@ -753,7 +745,7 @@ __global__ void __launch_bounds__(kSeqBlock) k_nice_spans(NiceArgs a, SpanTableP
 }
 
 template <bool ZF>
-__global__ void __launch_bounds__(kSeqBlock) k_pmosc_spans(PMOscArgs a, SpanTableP tb, Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(kSeqBlock) k_pmosc_spans(PMOscArgs a, NoteSpanTableP tb, Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
     const bool live = v0 < a.V;
     const uint32_t v = live ? v0 : 0;
@@ -781,9 +773,9 @@ __global__ void __launch_bounds__(kSeqBlock) k_pmosc_spans(PMOscArgs a, SpanTabl
 //     in every lane alike, reading frame j's input with a readlane and leaving (l, b, h) in LDS slot j;
 //     the input offset before it and the output mix after it are done for all 64 frames at once.
 // About 20 instructions per frame instead of 70.  Same per-voice operations in the same order => same
-// bits.  Sub-span semantics as in span_walk.
+// bits.  The sub-span walk is span_walk_wave's.
 template <bool ZF>
-__global__ void __launch_bounds__(64) k_nice_spans_wave(NiceArgs a, SpanTableP tb, Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(64) k_nice_spans_wave(NiceArgs a, NoteSpanTableP tb, Img out, uint32_t start, uint32_t end) {
     __shared__ float walk_s[64], svf_l[64], svf_b[64];
     const uint32_t v = blockIdx.x, lane = threadIdx.x;
     NiceLane n;
@@ -791,49 +783,33 @@ __global__ void __launch_bounds__(64) k_nice_spans_wave(NiceArgs a, SpanTableP t
     n.env.state = a.estate[v]; n.env.t = a.et[v]; n.env.last_value = a.elast[v]; n.env.start = a.estart[v];
     n.bad = true; n.k = PulseK{0, 0, 0.0f, 0.0f, 0.0f, 0.0f}; n.g = n.ng = 0.0f; n.cut = n.res = 0.0f;
     const float color = a.color[v];
-    const uint32_t cnt = min(tb.count[v], tb.K);
-    float *col = out.p + v;
-    const size_t os = out.stride;
-    auto zero = [&](uint32_t f0, uint32_t f1) ZH_INLINE_LAMBDA {
-        if (ZF) for (uint32_t f = f0 + lane; f < f1; f += 64) col[(size_t)f * os] = 0.0f;
-    };
-    uint32_t i = start;
-    for (uint32_t k = 0; k < cnt; k++) {
-        const size_t idx = (size_t)k * a.V + v;
-        const uint32_t s0 = tb.start[idx], s1 = tb.end[idx];
-        if (s0 < i || s0 > end) break;                          // never reached in order: nothing further fires
-        zero(i, s0);
-        n.begin(a.sample_rate, a.srf, a.sr8, tb.freq[idx], color, tb.note_on[idx] != 0, tb.nic[idx] != 0);
-        const bool ends = s1 >= s0 && s1 <= end;                // otherwise the sub-span runs to the buffer end
-        const uint32_t seg_end = ends ? s1 : end;
-        for (uint32_t f0 = s0; f0 < seg_end; f0 += 64) {
-            const uint32_t nf = min(64u, seg_end - f0);
-            const float t0_mine = n.osc(n.cnt + lane * n.k.ifreq);
-            if (!n.bad) n.cnt += nf * n.k.ifreq;
-            const float e0 = n.env.block64(nf, lane, walk_s);   // temps[0] = 0 (+ envelope)
-            // NiceLane::tail_filter with only svf_core on the chain: the input offset is added for all 64
-            // frames at once before it, the output mix after it from the captured (l, b, h) of each frame
-            const float in_mine = t0_mine + kSvfDcOffset;      // Filter.zig:135
-            auto step = [&](uint32_t j) ZH_INLINE_LAMBDA {
-                const SvfOut s = svf_core(n.l, n.b, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, in_mine), (int)j)), n.cut, n.res);
-                svf_l[j] = s.l; svf_b[j] = s.b;
-            };
-            uint32_t j = 0;
-            for (; j + 8 <= nf; j += 8) {
+    float *col = out.p + v;                                     // the voice's column, for the blocks' stores (span_walk_wave zeroes
+    const size_t os = out.stride;                               // the gaps of the same column of `out` itself)
+    span_walk_wave<ZF>(tb, a.V, v, lane, out, start, end,
+                       [&](size_t idx) ZH_INLINE_LAMBDA { n.begin(a.sample_rate, a.srf, a.sr8, tb.freq[idx], color, tb.note_on[idx] != 0, tb.nic[idx] != 0); },
+                       [&](uint32_t f0, uint32_t nf) ZH_INLINE_LAMBDA {
+        const float t0_mine = n.osc(n.cnt + lane * n.k.ifreq);
+        if (!n.bad) n.cnt += nf * n.k.ifreq;
+        const float e0 = n.env.block64(nf, lane, walk_s);   // temps[0] = 0 (+ envelope)
+        // NiceLane::tail_filter with only svf_core on the chain: the input offset is added for all 64
+        // frames at once before it, the output mix after it from the captured (l, b, h) of each frame
+        const float in_mine = t0_mine + kSvfDcOffset;      // Filter.zig:135
+        auto step = [&](uint32_t j) ZH_INLINE_LAMBDA {
+            const SvfOut s = svf_core(n.l, n.b, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, in_mine), (int)j)), n.cut, n.res);
+            svf_l[j] = s.l; svf_b[j] = s.b;
+        };
+        uint32_t j = 0;
+        for (; j + 8 <= nf; j += 8) {
 #pragma unroll
-                for (int q = 0; q < 8; q++) step(j + q);
-            }
-            for (; j < nf; j++) step(j);
-            if (lane < nf) {
-                const float t1 = svf_lowpass_into_zero(svf_l[lane], svf_b[lane]);   // temps[1] = 0 + low-pass
-                float *o = col + (size_t)(f0 + lane) * os;
-                *o = (ZF ? 0.0f : *o) + e0 * t1;               // multiply :246: out += temps[0]*temps[1]
-            }
+            for (int q = 0; q < 8; q++) step(j + q);
         }
-        i = seg_end;
-        if (!ends) break;
-    }
-    zero(i, end);
+        for (; j < nf; j++) step(j);
+        if (lane < nf) {
+            const float t1 = svf_lowpass_into_zero(svf_l[lane], svf_b[lane]);   // temps[1] = 0 + low-pass
+            float *o = col + (size_t)(f0 + lane) * os;
+            *o = (ZF ? 0.0f : *o) + e0 * t1;               // multiply :246: out += temps[0]*temps[1]
+        }
+    }, [&]() ZH_INLINE_LAMBDA {});
     if (lane == 0) {
         a.cnt[v] = n.cnt; a.fl[v] = n.l; a.fb[v] = n.b;
         a.estate[v] = n.env.state; a.et[v] = n.env.t; a.elast[v] = n.env.last_value; a.estart[v] = n.env.start;
@@ -847,46 +823,28 @@ __global__ void __launch_bounds__(64) k_nice_spans_wave(NiceArgs a, SpanTableP t
 // instructions per frame each) with lane j receiving frame j's values; then every lane evaluates
 // PMLane::value for its frame: the sines and the envelope curve, once per 64 frames instead of once per
 // frame.  Same per-voice operations in the same order => same bits.
-// Sub-span semantics are span_walk's: begin() at a sub-span's first frame, end() after its last,
-// nothing painted in between, a malformed table entry never fires.
+// The sub-span walk is span_walk_wave's.
 template <bool ZF>
-__global__ void __launch_bounds__(64) k_pmosc_spans_wave(PMOscArgs a, SpanTableP tb, Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(64) k_pmosc_spans_wave(PMOscArgs a, NoteSpanTableP tb, Img out, uint32_t start, uint32_t end) {
     __shared__ float walk_s[64];
     const uint32_t v = blockIdx.x, lane = threadIdx.x;
     PMLane n;
     pm_load(n, a, v);
     n.mod_freq = n.inv_sr = n.t_step = 0.0f;
     const float rel = a.release_duration[v];
-    const uint32_t cnt = min(tb.count[v], tb.K);
-    float *col = out.p + v;
-    const size_t os = out.stride;
-    auto zero = [&](uint32_t f0, uint32_t f1) ZH_INLINE_LAMBDA {
-        if (ZF) for (uint32_t f = f0 + lane; f < f1; f += 64) col[(size_t)f * os] = 0.0f;
-    };
-    uint32_t i = start;
-    for (uint32_t k = 0; k < cnt; k++) {
-        const size_t idx = (size_t)k * a.V + v;
-        const uint32_t s0 = tb.start[idx], s1 = tb.end[idx];
-        if (s0 < i || s0 > end) break;                          // never reached in order: nothing further fires
-        zero(i, s0);
-        n.begin(a.sample_rate, tb.freq[idx], rel, tb.note_on[idx] != 0, tb.nic[idx] != 0);
-        const bool ends = s1 >= s0 && s1 <= end;                // otherwise the sub-span runs to the buffer end, unfinished
-        const uint32_t seg_end = ends ? s1 : end;
-        for (uint32_t f0 = s0; f0 < seg_end; f0 += 64) {
-            const uint32_t nf = min(64u, seg_end - f0);
-            const float my_tm = zwalk64<true>(n.tm, n.mod_freq * n.inv_sr, 0, nf, lane, walk_s);   // PMLane::step_phase, 64 frames
-            const float my_tc = zwalk64<true>(n.tc, n.t_step, 0, nf, lane, walk_s);
-            const float my_e = n.env.block64(nf, lane, walk_s);                                      // PMLane::step_env
-            if (lane < nf) {
-                float *o = col + (size_t)(f0 + lane) * os;
-                *o = (ZF ? 0.0f : *o) + PMLane::value(my_tm, my_tc, my_e);
-            }
+    float *col = out.p + v;                                     // the voice's column, for the blocks' stores (span_walk_wave zeroes
+    const size_t os = out.stride;                               // the gaps of the same column of `out` itself)
+    span_walk_wave<ZF>(tb, a.V, v, lane, out, start, end,
+                       [&](size_t idx) ZH_INLINE_LAMBDA { n.begin(a.sample_rate, tb.freq[idx], rel, tb.note_on[idx] != 0, tb.nic[idx] != 0); },
+                       [&](uint32_t f0, uint32_t nf) ZH_INLINE_LAMBDA {
+        const float my_tm = zwalk64<true>(n.tm, n.mod_freq * n.inv_sr, 0, nf, lane, walk_s);   // PMLane::step_phase, 64 frames
+        const float my_tc = zwalk64<true>(n.tc, n.t_step, 0, nf, lane, walk_s);
+        const float my_e = n.env.block64(nf, lane, walk_s);                                      // PMLane::step_env
+        if (lane < nf) {
+            float *o = col + (size_t)(f0 + lane) * os;
+            *o = (ZF ? 0.0f : *o) + PMLane::value(my_tm, my_tc, my_e);
         }
-        i = seg_end;
-        if (!ends) break;
-        n.end();
-    }
-    zero(i, end);
+    }, [&]() ZH_INLINE_LAMBDA { n.end(); });
     if (lane == 0) pm_store(n, a, v);
 }
 
@@ -1666,17 +1624,10 @@ int zh_nice_paint_mix_stereo_batch(zh_nice *m, uint32_t start, uint32_t end, uin
     return nice_paint_mix_batch_impl(m, start, end, n_buffers, mix_left, mix_right, gain_left, gain_right, note_id_changed, params, flags);
 }
 
-static bool span_table_ok(const zh_span_table *t) {
-    return t && t->max_spans > 0 && t->count && t->start && t->end && t->freq && t->note_on && t->note_id_changed;
-}
-static SpanTableP mk_span_table(const zh_span_table *t) {
-    return SpanTableP{t->max_spans, t->count, t->start, t->end, t->freq, t->note_on, t->note_id_changed};
-}
-
 int zh_nice_paint_spans(zh_nice *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                         float sample_rate, const zh_span_table *table, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
-    if (!m || !outputs || end < start || !buf_covers(outputs[0], m->n, end) || !span_table_ok(table)) return ZH_ERR_INVALID;
+    if (!m || !outputs || end < start || !buf_covers(outputs[0], m->n, end) || !note_span_table_ok(table)) return ZH_ERR_INVALID;
     if (m->n == 0) return ZH_OK;
     hipStream_t st = m->ctx->stream;
     zh_nice_params p;
@@ -1687,10 +1638,10 @@ int zh_nice_paint_spans(zh_nice *m, uint32_t start, uint32_t end, const zh_buf *
     const bool zf = (flags & ZH_PAINT_ZERO_FIRST) != 0;
     const long wave_max = zh_form(ZF_NICE_WAVE_MAX);
     if ((long)m->n <= wave_max) {                            // few voices: one wave per voice, lanes = frames
-        if (zf) ZH_LAUNCH(k_nice_spans_wave<true>, dim3(m->n), dim3(64), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-        else ZH_LAUNCH(k_nice_spans_wave<false>, dim3(m->n), dim3(64), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-    } else if (zf) ZH_LAUNCH(k_nice_spans<true>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-    else ZH_LAUNCH(k_nice_spans<false>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
+        if (zf) ZH_LAUNCH(k_nice_spans_wave<true>, dim3(m->n), dim3(64), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+        else ZH_LAUNCH(k_nice_spans_wave<false>, dim3(m->n), dim3(64), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+    } else if (zf) ZH_LAUNCH(k_nice_spans<true>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+    else ZH_LAUNCH(k_nice_spans<false>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
     return zh_launch_status();
 }
 
@@ -2033,7 +1984,7 @@ int zh_pmosc_paint(zh_pmosc *m, uint32_t start, uint32_t end, const zh_buf *outp
 int zh_pmosc_paint_spans(zh_pmosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                          float sample_rate, const zh_span_table *table, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
-    if (!m || !outputs || end < start || !buf_covers(outputs[0], m->n, end) || !span_table_ok(table)) return ZH_ERR_INVALID;
+    if (!m || !outputs || end < start || !buf_covers(outputs[0], m->n, end) || !note_span_table_ok(table)) return ZH_ERR_INVALID;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
     hipStream_t st = m->ctx->stream;
@@ -2043,10 +1994,10 @@ int zh_pmosc_paint_spans(zh_pmosc *m, uint32_t start, uint32_t end, const zh_buf
     const bool zf = (flags & ZH_PAINT_ZERO_FIRST) != 0;
     const long wave_max = zh_form(ZF_PMOSC_WAVE_MAX);
     if ((long)m->n <= wave_max) {                            // few voices: one wave per voice, lanes = frames
-        if (zf) ZH_LAUNCH(k_pmosc_spans_wave<true>, dim3(m->n), dim3(64), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-        else ZH_LAUNCH(k_pmosc_spans_wave<false>, dim3(m->n), dim3(64), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-    } else if (zf) ZH_LAUNCH(k_pmosc_spans<true>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
-    else ZH_LAUNCH(k_pmosc_spans<false>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_table(table), mk_img(outputs[0]), start, end);
+        if (zf) ZH_LAUNCH(k_pmosc_spans_wave<true>, dim3(m->n), dim3(64), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+        else ZH_LAUNCH(k_pmosc_spans_wave<false>, dim3(m->n), dim3(64), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+    } else if (zf) ZH_LAUNCH(k_pmosc_spans<true>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
+    else ZH_LAUNCH(k_pmosc_spans<false>, seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_note_span_table(table), mk_img(outputs[0]), start, end);
     return zh_launch_status();
 }
 

@@ -89,8 +89,6 @@ int zh_store_mode() { const int m = zh_store_mode_env(); return m < 0 ? ST_SC1 :
 
 extern "C" {
 
-const char *zh_version(void) { return "zang_hip 0.1 (gfx950)"; }
-
 const char *zh_error_string(int err) {
     switch (err) {
     case ZH_OK: return "ok";

@@ -88,16 +88,8 @@ __global__ void __launch_bounds__(kSeqBlock) k_fm(FMArgs a, Img out, uint32_t st
     n.store_state(a.state, a.V, v);
 }
 
-// SpanTableP of composite.hip: the table as the walk reads it
-struct FMSpanTableP {
-    uint32_t K;
-    const uint32_t *count, *start, *end;
-    const float *freq;
-    const uint8_t *note_on, *nic;
-};
-
 template <bool ZF, bool SPLIT>
-__global__ void __launch_bounds__(kSeqBlock) k_fm_spans(FMArgs a, FMSpanTableP tb, Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(kSeqBlock) k_fm_spans(FMArgs a, NoteSpanTableP tb, Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
     const bool live = v0 < a.V;
     const uint32_t v = live ? v0 : 0;
@@ -108,7 +100,7 @@ __global__ void __launch_bounds__(kSeqBlock) k_fm_spans(FMArgs a, FMSpanTableP t
     const bool any3 = fm_any3(n);
     span_walk_segments(tb, a.V, v, live, start, end,
                        [&](size_t kv, bool nic) ZH_INLINE_LAMBDA { n.begin(a.sample_rate, tb.freq[kv], tb.note_on[kv] != 0, nic); },
-                       [&](uint32_t f0, uint32_t f1, bool active) ZH_INLINE_LAMBDA { fm_paint_frames<ZF, SPLIT>(n, out, v, a, j, f0, f1, active, any3); },
+                       [&](uint32_t f0, uint32_t f1, bool active) ZH_INLINE_LAMBDA { if (live) fm_paint_frames<ZF, SPLIT>(n, out, v, a, j, f0, f1, active, any3); },
                        [&]() ZH_INLINE_LAMBDA { n.end(); });
     if (live) n.store_state(a.state, a.V, v);
 }
@@ -239,15 +231,14 @@ int zh_fm_paint_spans(zh_fm *m, uint32_t start, uint32_t end, const zh_buf *outp
                       zh_buf tremolo_input, zh_buf vibrato_input, const zh_span_table *t, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
     if (!m || !outputs) return ZH_ERR_INVALID;
-    if (!t || t->max_spans == 0 || !t->count || !t->start || !t->end || !t->freq || !t->note_on || !t->note_id_changed) return ZH_ERR_INVALID;
+    if (!note_span_table_ok(t)) return ZH_ERR_INVALID;
     int rc = fm_paint_check(m, start, end, outputs, tremolo_input, vibrato_input, flags);
     if (rc) return rc;
     if (m->n == 0) return ZH_OK;
     hipStream_t st = m->ctx->stream;
     FMArgs a{m->state, m->tab, m->n, m->ni, m->group, sample_rate, mk_cimg(tremolo_input), mk_cimg(vibrato_input),
              F32P{0.0f, nullptr}, BoolP{0, nullptr}, BoolP{0, nullptr}};
-    const FMSpanTableP tb{t->max_spans, t->count, t->start, t->end, t->freq, t->note_on, t->note_id_changed};
-    ZH_FM_LAUNCH(k_fm_spans, a, tb, mk_img(outputs[0]), start, end);
+    ZH_FM_LAUNCH(k_fm_spans, a, mk_note_span_table(t), mk_img(outputs[0]), start, end);
     return zh_launch_status();
 }
 

@@ -6,6 +6,7 @@
 #include "zmath.hip.h"
 #include "dsp.hip.h"
 #include "seq.hip.h"
+#include "span_walk.hip.h"
 #include "envelope.hip.h"
 #include "voices.hip.h"
 
@@ -230,55 +231,28 @@ __device__ __forceinline__ bool zs_span_b(const zh_script_param &p, const zh_scr
 __device__ __forceinline__ uint32_t zs_span_tag(const zh_script_param &p, const zh_script_span_param &s, size_t kv) { return s.u ? s.u[kv] : p.u; }
 __device__ __forceinline__ float zs_span_payload(const zh_script_param &p, const zh_script_span_param &s, size_t kv) { return s.f ? s.f[kv] : p.f; }
 
-// The walk of composite.hip span_walk over a script module's frame loop: one lane per voice, and the wave walks the buffer in
-// segments that end at the next sub-span boundary of ANY of its lanes (a wave-wide minimum over all 64 lanes, taken before any
-// divergent branch).  Inside a segment no lane starts or ends a sub-span: the lanes inside one run zs_frame_loop over it, the
-// others store zeros (ZH_PAINT_ZERO_FIRST) or nothing.  begin(kv) runs the module's per-paint prologue for the lane's sub-span
-// at [k][v] at its first frame -- with only the lanes that start one there active, so a wave vote in a prologue (TriSawOscLane's
-// all_saw) speaks for those lanes, which is all the lanes that hold it read it for -- and end() its epilogue after its last.
+// The lane-per-voice walk of span_walk.hip.h (span_walk_segments: its contract, and segments that end at the next sub-span
+// boundary of ANY lane of the wave) over a script module's frame loop: inside a segment the lanes that are in a sub-span run
+// zs_frame_loop over it, the others store zeros (ZH_PAINT_ZERO_FIRST) or nothing.  begin(kv) runs the module's per-paint prologue
+// for the lane's sub-span at [k][v] at its first frame -- with only the lanes that start one there active, so a wave vote in a
+// prologue (TriSawOscLane's all_saw) speaks for those lanes, which is all the lanes that hold it read it for -- and end() its
+// epilogue after its last.
 // `live`: the lane owns a voice (a lane past the last voice walks with no sub-spans and stores nothing).
 template <int CH, int NIN, class B, class E, class F, class Q, class FQ>
 __device__ __forceinline__ void zs_span_walk(const ZsLaunch &L, const ZsSpans &S, uint32_t v, bool live, const float *const *in, const size_t *istride,
                                              const uint32_t *ivoff, bool &walk, B &&begin, E &&end_fn, F &&f, Q &&quiet, FQ &&fq) {
-    const uint32_t V = L.V;
     const bool zf = (L.flags & ZH_PAINT_ZERO_FIRST) != 0;
-    const uint32_t cnt = live ? min(S.t.count[v], S.t.max_spans) : 0u;
-    uint32_t k = 0, cur_end = 0;
-    uint32_t next_start = cnt > 0 ? S.t.start[v] : 0xffffffffu;
-    bool active = false;
-    auto advance = [&](uint32_t i) ZH_INLINE_LAMBDA {
-        for (;;) {
-            if (active) {
-                if (i != cur_end) break;
-                end_fn();
-                active = false;
-                k++;
-                next_start = k < cnt ? S.t.start[(size_t)k * V + v] : 0xffffffffu;
-                continue;
-            }
-            if (i != next_start) break;
-            const size_t kv = (size_t)k * V + v;
-            cur_end = S.t.end[kv];
-            begin(kv);
-            active = true;
-        }
-    };
-    uint32_t i = L.start;
-    while (i < L.end) {
-        advance(i);                                             // sub-spans that end / begin at frame i
-        uint32_t ev = active ? cur_end : next_start;            // this lane's next boundary (> i)
-        ev = (ev > i && ev < L.end) ? ev : L.end;               // unsorted / out-of-range entries never fire
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ev = min(ev, (uint32_t)__shfl_xor((int)ev, off));
-        const uint32_t seg_end = __builtin_amdgcn_readfirstlane(ev);
+    const bool zero_idle = zf && live;                              // a lane with a voice, outside its sub-spans, under ZH_PAINT_ZERO_FIRST
+    const SpanWalkP tb{S.t.max_spans, S.t.count, S.t.start, S.t.end, S.t.note_id_changed};
+    span_walk_segments(tb, L.V, v, live, L.start, L.end,
+                       [&](size_t kv, bool) ZH_INLINE_LAMBDA { begin(kv); },     // (the prologue reads note_id_changed itself)
+                       [&](uint32_t i, uint32_t seg_end, bool active) ZH_INLINE_LAMBDA {
         if (active) {
             zs_frame_loop<CH, NIN>(L.out, v, L.ostride, in, istride, ivoff, i, seg_end, zf, walk, f, quiet, fq);
-        } else if (zf && live) {
+        } else if (zero_idle) {
             for (uint32_t j = i; j < seg_end; j++) zrow_store<1>(zrow_rsrc(L.out, L.ostride, j), v * 4u, 0, 0.0f);
         }
-        i = seg_end;
-    }
-    advance(L.end);            // a sub-span that ends with the buffer; empty sub-spans at its end
+    }, end_fn);
 }
 
 // ---- the role-wave form of a generated kernel (zs_paint_pc_<name>; zscript_emit.hip plan_roles) -------------------------

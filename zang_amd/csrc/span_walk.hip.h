@@ -1,33 +1,44 @@
 // span_walk.hip.h -- the reference's Trigger loop (src/zang/trigger.zig:80-105; examples/example_song.zig:336-347) for one
-// voice per lane: every sub-span of a per-voice table is one paint(sub_span, ..., note_id_changed, params) call -- begin() at
-// its first frame, end() after its last, nothing painted between sub-spans.  The fused instruments' span paints
-// (composite.hip k_nice_spans / k_pmosc_spans) and the builtin modules' (k_<module>_spans, module_spans below) are built on it.
+// voice: every sub-span of a per-voice table is one paint(sub_span, ..., note_id_changed, params) call.  Two walks, one contract:
+// span_walk_segments (a lane per voice) under the fused instruments' span paints (composite.hip k_nice_spans / k_pmosc_spans,
+// fm.hip k_fm_spans), the builtin modules' (k_<module>_spans, module_spans below) and the generated kernels' (script_rt.hip.h
+// zs_span_walk); span_walk_wave (a wave per voice) under k_nice_spans_wave / k_pmosc_spans_wave.
 #pragma once
 #include "common.hip.h"
 #include "seq.hip.h"
 
-// The table as the walk reads it: device arrays [span][voice] (zh_span_table, zh_script_span_table)
+// The table as a walk reads it: device arrays [span][voice] (zh_script_span_table)
 struct SpanWalkP {
     uint32_t K;
     const uint32_t *count, *start, *end;
     const uint8_t *nic;
 };
+// ... with the note of each sub-span (zh_span_table): the fused instruments' tables (composite.hip, fm.hip)
+struct NoteSpanTableP {
+    uint32_t K;
+    const uint32_t *count, *start, *end;
+    const float *freq;
+    const uint8_t *note_on, *nic;
+};
 
-// The wave walks the buffer in segments that end at the next sub-span boundary of ANY of its lanes
+// THE CONTRACT of both walks below.  Sub-span k of voice v has its entries at kv = k * V + v; the first min(count[v], K) are read.
+// A sub-span begins (prologue) at its first frame and ends (epilogue) after its last; nothing is painted between sub-spans.  A
+// sub-span that starts before the previous one ends, before buf_start or after buf_end is never reached and ends the voice's
+// list; one that ends before it starts, or after buf_end, runs to the buffer end without its epilogue, and nothing follows it.
+
+// One voice per LANE.  The wave walks the buffer in segments that end at the next sub-span boundary of ANY of its lanes
 // (a wave-wide minimum): inside a segment no lane starts or ends a sub-span, so the frame loop is
 // the plain one of a module kernel with an `active` select -- checking every lane's boundaries on
 // every frame made the first span kernel 3x slower per frame than k_nice.  Boundaries mostly coincide
 // (every voice has one at each 1024-frame buffer edge), so segments are long.  `live` = the lane owns a
 // voice; all 64 lanes take part in the minimum.
-//   begin(kv, nic): sub-span k of voice v starts (kv = k * V + v: the index of its entries in the table)
-//   frame(x, val) -> painted: one frame of an active sub-span, x = the NIN input images' samples at the ABSOLUTE frame
+//   begin(kv, nic): sub-span k of voice v starts
+//   segment(i, seg_end, active): frames [i, seg_end); `active` = this lane is inside a sub-span there (only a live lane is).
+//   Called in EVERY lane: the callback keeps lanes that are not `live` from storing.
 //   end_fn(): the sub-span ended
-// A sub-span that starts before the previous one ends, or before buf_start, is never reached and ends the voice's list; one
-// that ends before it starts, or after buf_end, runs to the buffer end without its end().
-template <bool ZF, int NIN, class TB, class Begin, class Frame, class End>
-__device__ __forceinline__ void span_walk(const TB &tb, uint32_t V, uint32_t v, bool live, Img out, const float *const *in,
-                                          const size_t *istr, uint32_t buf_start, uint32_t buf_end, Begin &&begin, Frame &&frame,
-                                          End &&end_fn) {
+template <class TB, class Begin, class Segment, class End>
+__device__ __forceinline__ void span_walk_segments(const TB &tb, uint32_t V, uint32_t v, bool live, uint32_t buf_start, uint32_t buf_end,
+                                                   Begin &&begin, Segment &&segment, End &&end_fn) {
     const uint32_t cnt = live ? min(tb.count[v], tb.K) : 0;
     uint32_t k = 0, cur_end = 0;
     uint32_t next_start = cnt > 0 ? tb.start[v] : 0xffffffffu;
@@ -60,6 +71,20 @@ __device__ __forceinline__ void span_walk(const TB &tb, uint32_t V, uint32_t v, 
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) ev = min(ev, (uint32_t)__shfl_xor((int)ev, off));
         const uint32_t seg_end = __builtin_amdgcn_readfirstlane(ev);
+        segment(i, seg_end, active);
+        i = seg_end;
+    }
+    advance(buf_end);          // a sub-span that ends with the buffer; empty sub-spans at buf_end
+}
+
+// span_walk_segments over the frame loop of a module kernel (seq.hip.h frame_loop, 8-frame chunks):
+//   frame(x, val) -> painted: one frame of an active sub-span, x = the NIN input images' samples at the ABSOLUTE frame
+template <bool ZF, int NIN, class TB, class Begin, class Frame, class End>
+__device__ __forceinline__ void span_walk(const TB &tb, uint32_t V, uint32_t v, bool live, Img out, const float *const *in,
+                                          const size_t *istr, uint32_t buf_start, uint32_t buf_end, Begin &&begin, Frame &&frame,
+                                          End &&end_fn) {
+    span_walk_segments(tb, V, v, live, buf_start, buf_end, begin,
+                       [&](uint32_t i, uint32_t seg_end, bool active) ZH_INLINE_LAMBDA {
         if (live) {
             frame_loop<8, ZF, NIN>(out.p, v, out.stride, in, istr, i, seg_end,
                                    [&](uint32_t, const float (&x)[NIN > 0 ? NIN : 1], float &val) ZH_INLINE_LAMBDA {
@@ -67,56 +92,42 @@ __device__ __forceinline__ void span_walk(const TB &tb, uint32_t V, uint32_t v, 
                 return (bool)frame(x, val);
             });
         }
-        i = seg_end;
-    }
-    advance(buf_end);          // a sub-span that ends with the buffer; empty sub-spans at buf_end
+    }, end_fn);
 }
 
-// span_walk for a kernel that brings its own frame loop (fm.hip.h: per-instrument input columns, two output columns): the same
-// walk, with every segment handed over as a whole.
-//   segment(i, seg_end, active): frames [i, seg_end) -- no lane of the wave starts or ends a sub-span inside; `active` = this lane
-//   is inside a sub-span there.  Called in live lanes only.
-template <class TB, class Begin, class Segment, class End>
-__device__ __forceinline__ void span_walk_segments(const TB &tb, uint32_t V, uint32_t v, bool live, uint32_t buf_start, uint32_t buf_end,
-                                                   Begin &&begin, Segment &&segment, End &&end_fn) {
-    const uint32_t cnt = live ? min(tb.count[v], tb.K) : 0;
-    uint32_t k = 0, cur_end = 0;
-    uint32_t next_start = cnt > 0 ? tb.start[v] : 0xffffffffu;
-    bool active = false;
-    auto advance = [&](uint32_t i) ZH_INLINE_LAMBDA {
-        for (;;) {
-            if (active) {
-                if (i == cur_end) {
-                    end_fn(); active = false; k++;
-                    next_start = k < cnt ? tb.start[(size_t)k * V + v] : 0xffffffffu;
-                    continue;
-                }
-                break;
-            }
-            if (i == next_start) {
-                const size_t idx = (size_t)k * V + v;
-                cur_end = tb.end[idx];
-                begin(idx, tb.nic[idx] != 0);
-                active = true;
-                continue;
-            }
-            break;
-        }
+// One voice per WAVE, its lanes 64 consecutive frames (the fused instruments at a handful of voices: composite.hip
+// k_nice_spans_wave / k_pmosc_spans_wave).  Frames outside the sub-spans are zeroed here (ZF); a sub-span is handed over in
+// blocks of up to 64 frames.
+//   begin(kv): sub-span k starts (the kernel reads the table's other arrays at kv itself)
+//   block(f0, nf): frames [f0, f0 + nf), nf <= 64, lane j = frame f0 + j
+//   end_fn(): the sub-span ended
+template <bool ZF, class TB, class Begin, class Block, class End>
+__device__ __forceinline__ void span_walk_wave(const TB &tb, uint32_t V, uint32_t v, uint32_t lane, Img out, uint32_t buf_start,
+                                               uint32_t buf_end, Begin &&begin, Block &&block, End &&end_fn) {
+    const uint32_t cnt = min(tb.count[v], tb.K);
+    float *col = out.p + v;
+    const size_t os = out.stride;
+    auto zero = [&](uint32_t f0, uint32_t f1) ZH_INLINE_LAMBDA {
+        if (ZF) for (uint32_t f = f0 + lane; f < f1; f += 64) col[(size_t)f * os] = 0.0f;
     };
     uint32_t i = buf_start;
-    while (i < buf_end) {
-        advance(i);
-        uint32_t ev = active ? cur_end : next_start;
-        ev = (ev > i && ev < buf_end) ? ev : buf_end;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ev = min(ev, (uint32_t)__shfl_xor((int)ev, off));
-        const uint32_t seg_end = __builtin_amdgcn_readfirstlane(ev);
-        if (live) segment(i, seg_end, active);
+    for (uint32_t k = 0; k < cnt; k++) {
+        const size_t idx = (size_t)k * V + v;
+        const uint32_t s0 = tb.start[idx], s1 = tb.end[idx];
+        if (s0 < i || s0 > buf_end) break;                      // never reached in order: nothing further fires
+        zero(i, s0);
+        begin(idx);
+        const bool ends = s1 >= s0 && s1 <= buf_end;            // otherwise the sub-span runs to the buffer end, unfinished
+        const uint32_t seg_end = ends ? s1 : buf_end;
+        for (uint32_t f0 = s0; f0 < seg_end; f0 += 64) block(f0, min(64u, seg_end - f0));
         i = seg_end;
+        if (!ends) break;
+        end_fn();
     }
-    advance(buf_end);
+    zero(i, buf_end);
 }
 
+#if !defined(ZH_DEVICE_ONLY)   // the rest is the library's own: the generated kernels' runtime (hiprtc) takes the walks alone
 // One builtin module's span paint, one lane per voice (kSeqBlock-lane blocks over seq_grid(V)).  The adapter A wraps the
 // module's lane object (voices.hip.h):
 //   A::Args                          the kernel's argument block (a.V = voices); the per-sub-span arrays ride in it
@@ -155,14 +166,19 @@ __device__ __forceinline__ void module_spans(const typename A::Args &a, const Sp
 __device__ __forceinline__ float span_f(const float *arr, size_t kv, float dflt) { return arr ? arr[kv] : dflt; }
 __device__ __forceinline__ uint32_t span_u(const uint32_t *arr, size_t kv, uint32_t dflt) { return arr ? arr[kv] : dflt; }
 
-#if !defined(ZH_DEVICE_ONLY)
-// ---- host side of the builtin modules' span paints (zh_<m>_paint_spans)
+// ---- host side of the span paints (zh_<m>_paint_spans)
 enum { SPAN_F = 1, SPAN_U = 2 };   // which arrays a field takes
 static inline bool module_span_table_ok(const zh_script_span_table *t) {
     return t && t->max_spans > 0 && t->count && t->start && t->end && t->note_id_changed;
 }
 static inline SpanWalkP mk_span_walk(const zh_script_span_table *t) {
     return SpanWalkP{t->max_spans, t->count, t->start, t->end, t->note_id_changed};
+}
+static inline bool note_span_table_ok(const zh_span_table *t) {
+    return t && t->max_spans > 0 && t->count && t->start && t->end && t->freq && t->note_on && t->note_id_changed;
+}
+static inline NoteSpanTableP mk_note_span_table(const zh_span_table *t) {
+    return NoteSpanTableP{t->max_spans, t->count, t->start, t->end, t->freq, t->note_on, t->note_id_changed};
 }
 // every array of span_params (NULL = none) on a field that takes it
 static inline bool module_span_params_ok(const zh_script_span_param *sp, const uint8_t *kinds, int n) {
