@@ -492,6 +492,24 @@ ZH_API int zh_sampler_paint(zh_sampler *m, uint32_t span_start, uint32_t span_en
                             const zh_buf *temps, zh_bool note_id_changed,
                             const zh_sampler_params *params, uint32_t flags);                         /* :77-136 */
 
+/* A sample kit: K samples resident on the device, each with its own format, channel count, native rate and length (a drum
+ * machine's or a multi-sampled instrument's recordings: every Sampler instance of the reference holds its own Sample, and the
+ * sample is a Params field, Sampler.zig:62-67, so every note may pick another: examples/example_sampler.zig:86-91, :123-138).
+ * zh_sample_kit_create is THE ONE PLACE where zh_sample.data is read as a HOST pointer: the PCM bytes of samples[0..n) are
+ * copied into one device blob owned by the kit (every sample at a 4-byte-aligned offset; bytes after a sample's last whole
+ * frame are kept: they count in data_len for the wrap of :133-135 and are never decoded), with a descriptor table beside it.
+ * The call synchronises and is not capturable; the caller's arrays may be freed on return.  data_len == 0 is a valid, silent
+ * sample.  ZH_ERR_INVALID: n == 0, a format above ZH_SAMPLE_S32_LSB, num_channels == 0, data == NULL with data_len > 0, more
+ * than INT32_MAX frames (the reference's @intCast(i32, ...) traps, :42).  Destroy a kit after the last paint that reads it has
+ * run, and before its context.
+ * zh_sample_kit_sample fills a zh_sample whose `data` is the DEVICE pointer of entry i (valid while the kit lives): what
+ * zh_sampler_paint / zh_sampler_paint_spans take to play one entry of a kit. */
+typedef struct zh_sample_kit zh_sample_kit;
+ZH_API int zh_sample_kit_create(zh_ctx *ctx, const zh_sample *samples, uint32_t n, zh_sample_kit **out);
+ZH_API int zh_sample_kit_destroy(zh_sample_kit *kit);
+ZH_API int zh_sample_kit_count(const zh_sample_kit *kit, uint32_t *count_out);
+ZH_API int zh_sample_kit_sample(const zh_sample_kit *kit, uint32_t i, zh_sample *out);
+
 /* ---------------------------------------------------------------- Decimator (src/modules/Decimator.zig) */
 typedef struct zh_decimator zh_decimator;
 typedef struct zh_decimator_params { float sample_rate; uint32_t reserved; zh_buf input; zh_f32 fake_sample_rate; } zh_decimator_params; /* :5-9 */
@@ -913,6 +931,45 @@ ZH_API int zh_decimator_paint_spans(zh_decimator *m, uint32_t span_start, uint32
 ZH_API int zh_distortion_paint_spans(zh_distortion *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
                                      const zh_distortion_params *params, const zh_script_span_param *span_params /*[ZH_DISTORTION_SPAN_FIELDS]*/,
                                      const zh_script_span_table *table, uint32_t flags);
+
+/* The Sampler over a SAMPLE KIT: the sample and the channel are per-note values like every other Params field
+ * (Sampler.zig:62-67).  zh_sampler_paint_kit_spans is zh_sampler_paint_spans with two more span fields: for each voice v and
+ * k < min(count[v], max_spans), paint(sub_span_k, ..., note_id_changed[k][v], {sample_rate, kit[sample], channel, loop}_k) as
+ * the reference's Trigger loop hands each sub-span the sample of its own note (examples/example_sampler.zig:96-105), in one
+ * launch (k_sampler_kit_spans): each lane reads the descriptor of its own sample, the PCM format is a run-time value of the
+ * lane, and lanes of one wave take the plain (:105-114) and the resampling (:116-130) path at once.  The contract is that of
+ * the zh_<module>_paint_spans above -- empty sub-spans run their prologue, a sub-span out of order ends the voice's list,
+ * ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end), ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED, no host sync: capturable --
+ * except that NOTHING of the Sampler stays shared but the kit itself (one kit per call).  A field without a span array takes
+ * its value from `params`: a broadcast value or a per-voice device array.  Per sub-span, in the reference's order: channel >=
+ * the sample's num_channels paints nothing and leaves `t` alone, EVEN WHEN note_id_changed is set (:87-89 come before :91-93);
+ * a sample index >= the kit's count is DEFINED the same way (nothing painted, the state untouched, no memory read); then the
+ * reset of `t`, ratio = sample.sample_rate / sample_rate, the return for a negative ratio without loop, and the wrap by
+ * data.len in BYTES when looping (:133-135).  A sub-span may play another sample than the one before it with note_id_changed
+ * clear: `t` carries over, as in the reference.  State is the zh_sampler's `t` with the plain paints' bookkeeping: kit
+ * paints, plain paints, span paints and graph replays of one zh_sampler mix.
+ * zh_sampler_paint_kit is the uniform-span form: n Sampler instances, each with its own sample, channel, rate and loop flag,
+ * painting [span_start, span_end) in one launch of the same kernel.
+ * ZH_ERR_INVALID: what zh_<module>_paint_spans refuses, a NULL kit, a kit of another context, an output image that is NULL or
+ * too small. */
+typedef struct zh_u32 { uint32_t value; uint32_t reserved; const uint32_t *per_voice; } zh_u32;   /* broadcast, or device uint32[n_voices] */
+typedef struct zh_sampler_kit_params {
+    zh_f32 sample_rate;    /* the output rate (pitch; negative: backwards, examples/example_sampler.zig:131-137) */
+    zh_bool loop;
+    zh_u32 sample;         /* index into the kit */
+    zh_u32 channel;
+    const zh_sample_kit *kit;
+} zh_sampler_kit_params;
+enum { ZH_SAMPLER_KIT_SPAN_SAMPLE_RATE = 0,   /* f */
+       ZH_SAMPLER_KIT_SPAN_LOOP,              /* u (0 / non-zero) */
+       ZH_SAMPLER_KIT_SPAN_SAMPLE,            /* u */
+       ZH_SAMPLER_KIT_SPAN_CHANNEL,           /* u */
+       ZH_SAMPLER_KIT_SPAN_FIELDS };
+ZH_API int zh_sampler_paint_kit_spans(zh_sampler *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                      const zh_sampler_kit_params *params, const zh_script_span_param *span_params /*[ZH_SAMPLER_KIT_SPAN_FIELDS]*/,
+                                      const zh_script_span_table *table, uint32_t flags);
+ZH_API int zh_sampler_paint_kit(zh_sampler *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                zh_bool note_id_changed, const zh_sampler_kit_params *params, uint32_t flags);
 
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text

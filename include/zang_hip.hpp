@@ -114,6 +114,8 @@ public:
 // ---- values
 inline zh_f32 f32(float v) { return zh_f32{v, 0, nullptr}; }
 inline zh_f32 f32(const DeviceArray<float> &per_voice) { return zh_f32{0.0f, 0, per_voice.get()}; }
+inline zh_u32 u32(uint32_t v) { return zh_u32{v, 0, nullptr}; }
+inline zh_u32 u32(const DeviceArray<uint32_t> &per_voice) { return zh_u32{0, 0, per_voice.get()}; }
 inline zh_bool boolean(bool v) { return zh_bool{v ? 1u : 0u, 0, nullptr}; }
 inline zh_bool boolean(const DeviceArray<uint8_t> &per_voice) { return zh_bool{0, 0, per_voice.get()}; }
 
@@ -338,6 +340,23 @@ public:
     }
 };
 
+// K samples resident on the device (zh_sample_kit): `samples[i].data` are HOST pointers here, copied once; sample(i) hands entry i
+// back with its DEVICE pointer, for the plain Sampler paints.  Destroy it before its context.
+class SampleKit {
+    zh_sample_kit *h_ = nullptr;
+
+public:
+    SampleKit(Context &ctx, const std::vector<zh_sample> &samples) {
+        check(zh_sample_kit_create(ctx.get(), samples.data(), (uint32_t)samples.size(), &h_), "zh_sample_kit_create");
+    }
+    ~SampleKit() { if (h_) zh_sample_kit_destroy(h_); }
+    SampleKit(const SampleKit &) = delete;
+    SampleKit &operator=(const SampleKit &) = delete;
+    zh_sample_kit *get() const { return h_; }
+    uint32_t count() const { uint32_t n = 0; check(zh_sample_kit_count(h_, &n), "zh_sample_kit_count"); return n; }
+    zh_sample sample(uint32_t i) const { zh_sample s{}; check(zh_sample_kit_sample(h_, i, &s), "zh_sample_kit_sample"); return s; }
+};
+
 }  // namespace zang
 
 namespace mod {
@@ -405,6 +424,19 @@ ZANG_HIP_MODULE(PMOscInstrument, pmosc, 3, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32,
 #undef ZANG_HIP_USE_SEED
 #undef ZANG_HIP_COMMA_F32
 #undef ZANG_HIP_USE_F32
+
+// The Sampler over a sample kit: the sample and the channel are per-voice / per-note values like the rate and the loop flag
+// (Sampler.zig:62-67).  paintKit: n Samplers, each with its own sample, over one span; paintKitSpans: the Trigger loop, span_params
+// = host array [ZH_SAMPLER_KIT_SPAN_FIELDS] or nullptr.
+inline void paintKit(Sampler &m, zang::Span span, const std::array<zh_buf, 1> &outputs, zh_bool note_id_changed, const zh_sampler_kit_params &params,
+                     uint32_t flags = ZH_PAINT_ADD) {
+    zang::check(zh_sampler_paint_kit(m.get(), span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_sampler_paint_kit");
+}
+inline void paintKitSpans(Sampler &m, zang::Span span, const std::array<zh_buf, 1> &outputs, const zh_sampler_kit_params &params,
+                          const zh_script_span_param *span_params, const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+    zang::check(zh_sampler_paint_kit_spans(m.get(), span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags),
+                "zh_sampler_paint_kit_spans");
+}
 
 // NiceInstrument painted and mixed down over its voices without materialising per-voice output: mono, or two channels with a
 // per-voice gain each (a two-output module fed `voice * pan_c`, examples/example_stereo.zig:92-98)

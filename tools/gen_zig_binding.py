@@ -61,6 +61,9 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 # zh_<module>_paint_spans reads ZH_<MODULE>_SPAN_FIELDS entries
                 *[("zh_%s_paint_spans" % m, "span_params") for m in ("sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
                                                                      "filter", "sampler", "decimator", "distortion")],
+                ("zh_sampler_paint_kit_spans", "span_params"),
+                # n samples
+                ("zh_sample_kit_create", "samples"),
                 # the batch call reads n_buffers elements of each
                 ("zh_nice_paint_mix_stereo_batch", "note_id_changed"), ("zh_nice_paint_mix_stereo_batch", "params"),
                 # n_patches elements

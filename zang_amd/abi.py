@@ -120,6 +120,14 @@ class SamplerState(C.Structure):
     _fields_ = [("t", f32)]
 
 
+class U32(C.Structure):                    # zh_u32
+    _fields_ = [("value", u32), ("reserved", u32), ("per_voice", vp)]
+
+
+class SamplerKitParams(C.Structure):       # zh_sampler_kit_params
+    _fields_ = [("sample_rate", F32), ("loop", Bool), ("sample", U32), ("channel", U32), ("kit", vp)]
+
+
 class DecimatorParams(C.Structure):
     _fields_ = [("sample_rate", f32), ("reserved", u32), ("input", Buf), ("fake_sample_rate", F32)]
 
@@ -180,6 +188,7 @@ NOISE_SPAN_COLOR, NOISE_SPAN_FIELDS = range(2)
 GATE_SPAN_NOTE_ON, GATE_SPAN_FIELDS = range(2)
 FILTER_SPAN_TYPE, FILTER_SPAN_CUTOFF, FILTER_SPAN_RES, FILTER_SPAN_FIELDS = range(4)
 SAMPLER_SPAN_SAMPLE_RATE, SAMPLER_SPAN_LOOP, SAMPLER_SPAN_FIELDS = range(3)
+SAMPLER_KIT_SPAN_SAMPLE_RATE, SAMPLER_KIT_SPAN_LOOP, SAMPLER_KIT_SPAN_SAMPLE, SAMPLER_KIT_SPAN_CHANNEL, SAMPLER_KIT_SPAN_FIELDS = range(5)
 DECIMATOR_SPAN_FAKE_SAMPLE_RATE, DECIMATOR_SPAN_FIELDS = range(2)
 DISTORTION_SPAN_TYPE, DISTORTION_SPAN_INGAIN, DISTORTION_SPAN_OUTGAIN, DISTORTION_SPAN_OFFSET, DISTORTION_SPAN_FIELDS = range(5)
 
@@ -436,6 +445,12 @@ SIGNATURES = {
     "zh_sampler_get_state": (C.c_int, [vp, vp]),
     "zh_sampler_set_state": (C.c_int, [vp, vp]),
     "zh_sampler_paint": (C.c_int, _paint(SamplerParams)),
+    "zh_sample_kit_create": (C.c_int, [vp, P(Sample), u32, P(vp)]),
+    "zh_sample_kit_destroy": (C.c_int, [vp]),
+    "zh_sample_kit_count": (C.c_int, [vp, P(u32)]),
+    "zh_sample_kit_sample": (C.c_int, [vp, u32, P(Sample)]),
+    "zh_sampler_paint_kit_spans": (C.c_int, _paint_spans(SamplerKitParams)),
+    "zh_sampler_paint_kit": (C.c_int, _paint(SamplerKitParams)),
     "zh_decimator_create": (C.c_int, [vp, u32, P(vp)]),
     "zh_decimator_destroy": (C.c_int, [vp]),
     "zh_decimator_get_state": (C.c_int, [vp, vp]),

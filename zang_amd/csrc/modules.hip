@@ -15,6 +15,7 @@
 #include "envelope.hip.h"
 #include "voices.hip.h"
 #include "span_walk.hip.h"
+#include "sample_kit.hip.h"
 #define ZH_FILTER_TP_PINK 1
 #include "filter_tp.hip.h"
 #include <vector>
@@ -936,6 +937,14 @@ struct zh_sampler : zh_flipper {
 };
 
 // (SampleP and the sample reads live in voices.hip.h, next to SamplerLane)
+// K samples on the device (sample_kit.hip.h has the layout and the lane that reads it)
+struct zh_sample_kit {
+    zh_ctx *ctx;
+    uint32_t n;
+    uint8_t *blob;
+    ZkSampleDesc *desc;
+    std::vector<zh_sample> samples;      // the entries as zh_sample_kit_sample hands them out: `data` points into the blob
+};
 
 // One kernel, two launch shapes.  Sequential: grid.y = 1, ch = the whole span, t_in == t_out.  Few voices: grid.y frame
 // ranges of `ch` frames at once, one wave per (64 voices, range) -- the play position that reaches frame f0 is the start
@@ -1939,6 +1948,47 @@ int zh_atan(zh_ctx *ctx, uint32_t n, float *out, const float *x) { ZH_GUARD(ctx)
 }
 
 // ------------------------------------------------------------------ Sampler
+// zh_sample_kit: zk_describe / zk_pack (sample_kit.hip.h) lay the samples out on the host, one copy takes the blob over
+int zh_sample_kit_create(zh_ctx *ctx, const zh_sample *samples, uint32_t n, zh_sample_kit **out) { ZH_GUARD(ctx);
+    if (!ctx || !out) return ZH_ERR_INVALID;
+    if (ctx->capturing) return ZH_ERR_UNSUPPORTED;                                   // the copy synchronises
+    std::vector<ZkSampleDesc> desc(n);
+    size_t bytes = 0;
+    int rc = zk_describe(samples, n, desc.data(), &bytes);
+    if (rc) return rc;
+    std::vector<uint8_t> blob(bytes);
+    zk_pack(samples, n, desc.data(), blob.data(), bytes);
+    zh_sample_kit *k = new (std::nothrow) zh_sample_kit();
+    if (!k) return ZH_ERR_INVALID;
+    k->ctx = ctx; k->n = n; k->blob = nullptr; k->desc = nullptr;
+    k->samples.assign(samples, samples + n);
+    rc = dev_alloc(&k->blob, bytes);
+    if (!rc) rc = dev_alloc(&k->desc, n);
+    if (!rc) rc = zh_upload(ctx, k->blob, blob.data(), bytes);
+    if (!rc) rc = zh_upload(ctx, k->desc, desc.data(), (size_t)n * sizeof(ZkSampleDesc));
+    if (rc) { (void)hipFree(k->blob); (void)hipFree(k->desc); delete k; return rc; }
+    for (uint32_t i = 0; i < n; i++) { k->samples[i].data = k->blob + desc[i].offset; k->samples[i].reserved = 0; }
+    *out = k;
+    return ZH_OK;
+}
+int zh_sample_kit_destroy(zh_sample_kit *kit) { ZH_GUARD(kit ? kit->ctx : nullptr);
+    if (!kit) return ZH_ERR_INVALID;
+    (void)hipStreamSynchronize(kit->ctx->stream);
+    (void)hipFree(kit->blob); (void)hipFree(kit->desc);
+    delete kit;
+    return ZH_OK;
+}
+int zh_sample_kit_count(const zh_sample_kit *kit, uint32_t *count_out) {
+    if (!kit || !count_out) return ZH_ERR_INVALID;
+    *count_out = kit->n;
+    return ZH_OK;
+}
+int zh_sample_kit_sample(const zh_sample_kit *kit, uint32_t i, zh_sample *out) {
+    if (!kit || !out || i >= kit->n) return ZH_ERR_INVALID;
+    *out = kit->samples[i];
+    return ZH_OK;
+}
+
 int zh_sampler_create(zh_ctx *ctx, uint32_t n, zh_sampler **out) { ZH_GUARD(ctx); return flip1_create(ctx, n, out); }   // init() :71-75
 int zh_sampler_destroy(zh_sampler *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip1_destroy(m); }
 int zh_sampler_get_state(zh_sampler *m, zh_sampler_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
@@ -2461,6 +2511,45 @@ template <int FMT> struct SamplerSpans {
 };
 ZH_MODULE_SPANS_KERNEL(k_sampler_spans)
 
+// ---- Sampler over a sample kit: the sample and the channel per sub-span too (SamplerKitLane: the lane's own descriptor and
+// a run-time format); ONE instantiation for every format.
+struct SamplerKitSpanArgs {
+    uint32_t V; const float *t_in; float *t_out; const uint8_t *blob; const ZkSampleDesc *desc; uint32_t count;
+    F32P rate; BoolP loop; ZkU32P sample, channel; const float *sr; const uint32_t *sl, *ss, *sc;
+};
+struct SamplerKitSpans {
+    using Args = SamplerKitSpanArgs;
+    static constexpr int NIN = 0;
+    SamplerKitLane o;
+    float rate0;
+    uint32_t loop0, sample0, channel0;
+    __device__ __forceinline__ void load(const Args &a, uint32_t v) {
+        o.idle();
+        o.t = a.t_in[v]; rate0 = a.rate.get(v); loop0 = a.loop.get(v) ? 1u : 0u; sample0 = a.sample.get(v); channel0 = a.channel.get(v);
+    }
+    __device__ __forceinline__ void inputs(const Args &, const float **, size_t *) const {}
+    __device__ __forceinline__ void begin(const Args &a, size_t kv, bool nic) {
+        o.begin(a.desc, a.count, span_u(a.ss, kv, sample0), span_u(a.sc, kv, channel0), span_f(a.sr, kv, rate0), span_u(a.sl, kv, loop0) != 0, nic);
+    }
+    template <int NI> __device__ __forceinline__ bool frame(const Args &a, const float (&)[NI], float &val) { return o.frame(a.blob, val); }
+    __device__ __forceinline__ void end(const Args &) { o.end(); }
+    __device__ __forceinline__ void store(const Args &a, uint32_t v) const { a.t_out[v] = o.t; }
+};
+ZH_MODULE_SPANS_KERNEL(k_sampler_kit_spans)
+// zh_sampler_paint_kit: every voice has ONE sub-span, the span itself, with its own note_id_changed -- the same walk, adapter
+// and frame body over a table that holds no arrays
+struct OneSpanWalkP {
+    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
+    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
+    uint32_t K;
+    U32 count, start, end;
+    Nic nic;                                                           // kv = 0 * V + v
+};
+template <bool ZF, class A>
+__global__ void __launch_bounds__(kSeqBlock) k_sampler_kit(const typename A::Args a, const OneSpanWalkP tb, const Img out, uint32_t start, uint32_t end) {
+    module_spans<ZF, A>(a, tb, out, start, end);
+}
+
 // ---- Decimator: the fake sample rate per sub-span (DecimatorLane::frame paints nothing in mode 2)
 struct DecSpanArgs { uint32_t V; const float *dval_in, *dcount_in; float *dval_out, *dcount_out; CImg input; float sample_rate; F32P fake; const float *sf; };
 struct DecSpans {
@@ -2629,6 +2718,54 @@ int zh_sampler_paint_spans(zh_sampler *m, uint32_t start, uint32_t end, const zh
     case ZH_SAMPLE_S24_LSB: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_S24_LSB>); break;
     default: ZH_MODULE_SPANS_LAUNCH(k_sampler_spans, SamplerSpans<ZH_SAMPLE_S32_LSB>); break;
     }
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+// what both kit paints check after the common checks, and the kernel's arguments
+static int sampler_kit_args(zh_sampler *m, const zh_sampler_kit_params *p, const zh_script_span_param *sp, SamplerKitSpanArgs &a) {
+    if (!p->kit || p->kit->ctx != m->ctx) return ZH_ERR_INVALID;
+    a = SamplerKitSpanArgs{m->n, m->t(), reinterpret_cast<float *>(m->cnt[m->cur ^ 1]), p->kit->blob, p->kit->desc, p->kit->n,
+                           mk_f32(p->sample_rate), mk_bool(p->loop), ZkU32P{p->sample.value, p->sample.per_voice},
+                           ZkU32P{p->channel.value, p->channel.per_voice}, span_fa(sp, ZH_SAMPLER_KIT_SPAN_SAMPLE_RATE),
+                           span_ua(sp, ZH_SAMPLER_KIT_SPAN_LOOP), span_ua(sp, ZH_SAMPLER_KIT_SPAN_SAMPLE), span_ua(sp, ZH_SAMPLER_KIT_SPAN_CHANNEL)};
+    return ZH_OK;
+}
+
+int zh_sampler_paint_kit_spans(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                               const zh_sampler_kit_params *p, const zh_script_span_param *sp, const zh_script_span_table *table,
+                               uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    ZH_SPANS_COMMON_CHECKS(ZH_SAMPLER_KIT_SPAN_FIELDS, SPAN_F, SPAN_U, SPAN_U, SPAN_U);
+    SamplerKitSpanArgs a;
+    if ((rc = sampler_kit_args(m, p, sp, a))) return rc;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from, flip or not (ctx.hip)
+    const bool zf = flags & ZH_PAINT_ZERO_FIRST;
+    hipStream_t st = m->ctx->stream;
+    ZH_MODULE_SPANS_LAUNCH(k_sampler_kit_spans, SamplerKitSpans);
+    zh_flipper_painted(m);
+    m->cur ^= 1;
+    return zh_launch_status();
+}
+
+int zh_sampler_paint_kit(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
+                         zh_bool note_id_changed, const zh_sampler_kit_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    (void)temps;
+    int rc = paint_check(m, start, end, outputs);
+    if (rc) return rc;
+    if (!p) return ZH_ERR_INVALID;
+    SamplerKitSpanArgs a;
+    if ((rc = sampler_kit_args(m, p, nullptr, a))) return rc;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (m->n == 0) return ZH_OK;
+    zh_flipper_used(m);
+    const OneSpanWalkP tb{1, {1}, {start}, {end}, {mk_bool(note_id_changed)}};
+    const dim3 grid = seq_grid(m->n);
+    hipStream_t st = m->ctx->stream;
+    if (flags & ZH_PAINT_ZERO_FIRST) ZH_LAUNCH((k_sampler_kit<true, SamplerKitSpans>), grid, dim3(kSeqBlock), 0, st, a, tb, mk_img(outputs[0]), start, end);
+    else ZH_LAUNCH((k_sampler_kit<false, SamplerKitSpans>), grid, dim3(kSeqBlock), 0, st, a, tb, mk_img(outputs[0]), start, end);
     zh_flipper_painted(m);
     m->cur ^= 1;
     return zh_launch_status();

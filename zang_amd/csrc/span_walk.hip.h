@@ -136,8 +136,9 @@ __device__ __forceinline__ void span_walk_wave(const TB &tb, uint32_t V, uint32_
 //   inputs(a, in, istr)              the NIN input images
 //   begin(a, kv, nic) / frame(a, x, val) -> painted / end(a)   one paint() call's prologue, frames and epilogue
 // Idle lanes of the last wave shadow voice 0 read-only and store nothing.
-template <bool ZF, class A>
-__device__ __forceinline__ void module_spans(const typename A::Args &a, const SpanWalkP &tb, Img out, uint32_t start, uint32_t end) {
+// TB: the table, SpanWalkP or anything that reads like it (modules.hip OneSpanWalkP: one sub-span per voice, no arrays).
+template <bool ZF, class A, class TB>
+__device__ __forceinline__ void module_spans(const typename A::Args &a, const TB &tb, Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
     const bool live = v0 < a.V;
     const uint32_t v = live ? v0 : 0;

@@ -16,7 +16,7 @@ from typing import Any
 import numpy as np
 
 from . import abi
-from .runtime import as_bool, as_buf, as_f32, default_context
+from .runtime import as_bool, as_buf, as_f32, as_u32, default_context
 
 
 def _bufarray(tensors):
@@ -339,6 +339,52 @@ class Sampler(_Module):
 
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
         self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
+
+    # ---- over a sample kit (zang_amd.samplekit.SampleKit): the sample and the channel are per-voice / per-note values too
+    @dataclass
+    class KitParams:
+        kit: Any            # SampleKit
+        sample_rate: Any    # float, or float32 CUDA tensor [n_voices]
+        sample: Any         # int, or int32 CUDA tensor [n_voices]: the index into the kit
+        channel: Any = 0    # int, or int32 CUDA tensor [n_voices]
+        loop: Any = False   # bool, or uint8 / bool CUDA tensor [n_voices]
+
+    _kit_span_fields = (("sample_rate", "constant"), ("loop", "boolean"), ("sample", "tag"), ("channel", "tag"))
+
+    @classmethod
+    def kit_span_table(cls, count, start, end, note_id_changed, values=None):
+        """span_table() for paint_kit_spans: `values` {field of _kit_span_fields: (f [K][V] or None, u [K][V] or None)}"""
+        from .script import ScriptSpanTable
+        return ScriptSpanTable([(n, k, None) for n, k in cls._kit_span_fields], count, start, end, note_id_changed, values)
+
+    @staticmethod
+    def _kit_cparams(params):
+        return abi.SamplerKitParams(as_f32(params.sample_rate), as_bool(params.loop), as_u32(params.sample), as_u32(params.channel),
+                                    params.kit.handle)
+
+    def paint_kit(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+        """n Sampler instances, each with its own sample, channel, rate and loop flag (KitParams), in one paint (zh_sampler_paint_kit)"""
+        cp = self._kit_cparams(params)
+        rc = self.lib.zh_sampler_paint_kit(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps), as_bool(note_id_changed),
+                                           C.byref(cp), abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, "zh_sampler_paint_kit")
+
+    def paint_kit_spans(self, span, outputs, temps, params, table, zero_first=False):
+        """paint_spans with the note's sample and channel among the per-sub-span values (zh_sampler_paint_kit_spans): `params` a
+        KitParams for the fields `table` holds no array for; `table` from kit_span_table() or a voice bank's script_table()."""
+        rc = self._paint_kit_spans(span, outputs, temps, params, table, abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, "zh_sampler_paint_kit_spans")
+
+    def _paint_kit_spans(self, span, outputs, temps, params, table, flags, span_params=None):
+        """-> the return code; `span_params`: a ctypes ScriptSpanParam array to pass instead of the table's (the error tests)"""
+        cp = self._kit_cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._kit_span_fields])
+        if span_params is not None:
+            sp = span_params
+        rc = self.lib.zh_sampler_paint_kit_spans(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps), C.byref(cp), sp,
+                                                 C.byref(tb), flags)
+        self._keep = (cp, outputs, table, params)
+        return rc
 
 
 class Decimator(_Module):

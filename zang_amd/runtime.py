@@ -157,6 +157,19 @@ def as_f32(x):
     return abi.F32(float(x), 0, None)
 
 
+def as_u32(x):
+    """int, or int32 CUDA tensor [n_voices] (torch has no uint32 arithmetic: the bits are read as uint32) -> zh_u32."""
+    if isinstance(x, abi.U32):
+        return x
+    if isinstance(x, torch.Tensor):
+        if not (x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("per-voice u32 parameter must be a contiguous int32 CUDA tensor [n_voices]")
+        u = abi.U32(0, 0, x.data_ptr())
+        u._keep = x
+        return u
+    return abi.U32(int(x), 0, None)
+
+
 def as_bool(x):
     """bool, or uint8/bool CUDA tensor [n_voices] -> zh_bool."""
     if isinstance(x, abi.Bool):
