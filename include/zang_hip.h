@@ -533,7 +533,12 @@ ZH_API int zh_distortion_paint(zh_distortion *m, uint32_t span_start, uint32_t s
                                const zh_distortion_params *params, uint32_t flags);                   /* :27-66 */
 
 /* ---------------------------------------------------------------- Curve (src/modules/Curve.zig)
- * (entry points are named zh_curve_module_* because zh_curve is zang.PaintCurve) */
+ * (entry points are named zh_curve_module_* because zh_curve is zang.PaintCurve)
+ * Node times may be any f32: a time becomes a frame through the saturating conversion (NaN -> 0) and is only ever compared with
+ * frames of the span, never used as an address; where the difference of two such frames leaves i32 (a checked-arithmetic panic
+ * in the reference) it wraps.
+ * The node carried over from the previous paint is read at the index that paint left (current_song_note), whatever curve_len is
+ * now: do not pass a shorter node list without note_id_changed (which restarts at node 0). */
 typedef struct zh_curve_module zh_curve_module;
 enum { ZH_CURVE_FN_LINEAR = 0, ZH_CURVE_FN_SMOOTHSTEP = 1 };                                          /* :4-7 */
 typedef struct zh_curve_node { float value, t; } zh_curve_node;                                       /* zang.CurveNode, src/zang/curve.zig:3-6 */

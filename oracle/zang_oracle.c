@@ -857,10 +857,13 @@ void zo_curve_paint(zo_curve_module *self, size_t span_start, size_t span_end, f
         if (cs.has_values) {
             const int32_t paint_start = (int32_t)cs.start;
             const int32_t fstart = cs.a.frame, fend = cs.b.frame;
-            const float start_x = (float)(paint_start - fstart) / (float)(fend - fstart);   /* :95 */
+            /* Node frames come from a saturating conversion (a node at a huge, infinite or NaN time): their differences can
+             * leave i32, a checked-arithmetic panic in the reference.  DEFINED: they wrap (two's complement), here and on the device. */
+            const int32_t dx = (int32_t)((uint32_t)paint_start - (uint32_t)fstart), df = (int32_t)((uint32_t)fend - (uint32_t)fstart);
+            const float start_x = (float)dx / (float)df;             /* :95 */
             const float start_value = cs.a.value;
             const float value_delta = cs.b.value - cs.a.value;
-            const float x_step = 1.0f / (float)(fend - fstart);      /* :100 */
+            const float x_step = 1.0f / (float)df;                   /* :100 */
             if (function == ZO_CURVE_FN_LINEAR) {
                 float y = start_value + start_x * value_delta;
                 const float y_step = x_step * value_delta;

@@ -234,3 +234,53 @@ def test_paint_kit_spans_builds_the_ctypes_arguments_without_a_device():
         assert sp[i].f is None and sp[i].u is None
     with pytest.raises(KeyError):
         m.kit_span_table(np.ones(3), np.zeros((1, 3)), np.full((1, 3), 64), np.zeros((1, 3)), {"cutoff": (np.ones((1, 3)), None)})
+
+
+# ------------------------------------------------------------------ hostile rates and play positions
+# The rate reaches an address: ratio = sample.sample_rate / rate steps the play position t, and floor(t) / round(t) index the PCM.
+# Why no f32 rate or position can take a load outside the sample (csrc/voices.hip.h, csrc/modules.hip k_sampler, csrc/sample_kit.hip.h):
+#   * the position becomes an index only through zf32_to_i32, which saturates at +-2^31 and takes NaN to 0; t0 + n and i0 + 1 are
+#     formed in uint32, so they wrap instead of overflowing;
+#   * every PCM load goes through sampler_at, whose address is (0 <= index < num_samples ? index : 0) * num_channels + channel with
+#     channel < num_channels checked on the host, or through the paired load of k_sampler, whose frame is min(max(r0, 0), n - 2) with
+#     n >= 2 required for that path; an index outside the sample selects the value 0 AFTER a load from frame 0;
+#   * a looped index goes through sampler_mod first, whose result is corrected into [0, n) -- and sampler_at tests it again;
+#   * a sample without frames is the format kSampleEmpty, which loads nothing;
+#   * every loop runs over the span's frames; none is bounded by t or the ratio.
+# Here the lane runs them under ASan / UBSan against the oracle.
+HOSTILE_RATES = [np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-45, -1e-40, 1e-30, 3e38, -3e38, -1.0, 1.0, 2.0, 1e9, 4.3e9,
+                 44100.0 / 0.9999, 44100.0 / 1.0001, 44095.59, 44104.41]
+HOSTILE_T = [np.nan, np.inf, -np.inf, 3e38, -3e38, 2.0 ** 31, -2.0 ** 31, 2.0 ** 31 - 128, 1e-45, -0.0, -0.5, 4.3e9]
+
+
+def _same_f32(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+@pytest.mark.parametrize("zero_first", [False, True], ids=["add", "zero_first"])
+def test_lane_with_hostile_rates_and_positions_equals_the_oracle(harness, oracle, tmp_path, zero_first):
+    """Every hostile rate in a sub-span of every kit sample, looped and not, from ordinary and hostile play positions, over two
+    carried buffers: no sanitizer report, NaN positions equal, every other sample and `t` bit for bit."""
+    samples = sk.kit_samples()
+    V = 8 * len(HOSTILE_RATES)
+    rng = np.random.default_rng(77)
+    t_ref = sk.start_t(V, 5)
+    t_ref[4:4 + len(HOSTILE_T)] = HOSTILE_T
+    t_got = t_ref.copy()
+    painted = 0
+    for b in range(2):
+        tb = sk.tables(V, 900 + b, second=b == 1)
+        v = np.arange(V)
+        for k in range(sk.MAX_SPANS):
+            hit = (v + k) % 2 == 0                                   # every other sub-span of a voice keeps its ordinary rate
+            tb["sample_rate"][k, hit] = np.array(HOSTILE_RATES, np.float32)[(v[hit] // 8 + k) % len(HOSTILE_RATES)]
+        base = rng.uniform(-1.0, 1.0, (V, sk.ROWS)).astype(np.float32)
+        ref, t_ref = sk.reference(oracle, samples, tb, t_ref, base.copy(), zero_first)
+        got, t_got = sk.run_lane_harness(harness, str(tmp_path), samples, tb, t_got, base.copy(), zero_first)
+        assert _same_f32(got, ref), (b, np.argwhere(got.view(np.uint32) != ref.view(np.uint32))[:5])
+        assert _same_f32(t_got, t_ref), (b, t_got, t_ref)
+        painted += int((ref != base).sum())
+        assert np.isnan(ref).mean() <= 0.5
+    assert painted > 0

@@ -267,10 +267,15 @@ struct DecimatorLane {
         dcount = trig ? dc - 1.0f : dc;
         last = trig ? i : last;
     }
-    // step() for 0 <= dcount <= 1 and 0 < ratio < 1 (every state the module itself produces): then dcount + ratio is below 2 and
-    // `dc >= 1 ? dc - 1 : dc` is dc - floor(dc), one v_fract_f32 (exact: the subtraction of 1 from a value in [1, 2) is); the
-    // frame index rides in a VGPR so that the whole step is five VALU instructions and no scalar ones
-    __device__ __forceinline__ bool walk_is_plain() const { return mode != 1 || (dcount >= 0.0f && dcount <= 1.0f && ratio > 0.0f && ratio < 1.0f); }
+    // step() for 0 <= dcount <= 1, 0 < ratio < 1 and a first sum below 2 (every state the module itself produces, but for one
+    // ratio): then every dcount + ratio is below 2 and `dc >= 1 ? dc - 1 : dc` is dc - floor(dc), one v_fract_f32 (exact: the
+    // subtraction of 1 from a value in [1, 2) is); the frame index rides in a VGPR so that the whole step is five VALU instructions
+    // and no scalar ones.  The first sum is tested because it alone can ROUND to 2: dcount == 1 (init, or after a buffer with
+    // fake >= sample_rate) with ratio == 1 - 2^-24 (fake one ulp below the sample rate) is a tie, 2.0 after rounding, where the
+    // reference's dc - 1 is 1 and fract is 0.  After any step dcount is below 1, and two floats below 1 sum to 2 - 2^-23 at most.
+    __device__ __forceinline__ bool walk_is_plain() const {
+        return mode != 1 || (dcount >= 0.0f && dcount <= 1.0f && ratio > 0.0f && ratio < 1.0f && dcount + ratio < 2.0f);
+    }
     __device__ __forceinline__ void step_plain(uint32_t &idx, uint32_t &last) {
         const float dc = dcount + ratio;
         last = dc >= 1.0f ? idx : last;
@@ -528,10 +533,12 @@ struct CurveLane {
         if (a.frame > (int32_t)dest_start) add_span(tb, (uint32_t)a.frame, false, 0.0f, 0.0f, 0.0f, 0.0f);   // the gap before the node
         float acc_ = 0.0f, step_ = 0.0f, sv_ = 0.0f, vd_ = 0.0f;
         if (has_b) {                                                                                    // :84-107
-            const float start_x = (float)((int32_t)dest_start - a.frame) / (float)(b.frame - a.frame);   // :95
+            // (frames of saturated node times: the differences WRAP, as the oracle defines them -- no signed overflow for the compiler)
+            const int32_t dx = (int32_t)(dest_start - (uint32_t)a.frame), df = (int32_t)((uint32_t)b.frame - (uint32_t)a.frame);
+            const float start_x = (float)dx / (float)df;                                                 // :95
             sv_ = a.value;
             vd_ = b.value - a.value;
-            const float x_step = 1.0f / (float)(b.frame - a.frame);                                     // :100
+            const float x_step = 1.0f / (float)df;                                                      // :100
             if (function == ZH_CURVE_FN_LINEAR) { acc_ = sv_ + start_x * vd_; step_ = x_step * vd_; }
             else { acc_ = start_x; step_ = x_step; }
         }
