@@ -976,6 +976,76 @@ ZH_API int zh_sampler_paint_kit_spans(zh_sampler *m, uint32_t span_start, uint32
 ZH_API int zh_sampler_paint_kit(zh_sampler *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
                                 zh_bool note_id_changed, const zh_sampler_kit_params *params, uint32_t flags);
 
+/* ---------------------------------------------------------------- sound-effect voice (examples/example_laser.zig:22-117)
+ * LaserPlayer as ONE kernel: three Curves (modulator frequency, carrier frequency, volume) drive a phase-modulated pair of
+ * SineOscs; a one-shot effect fired by an impulse, no note-off.  Bit-identical to the reference's stage order, per sub-span
+ * (Cm, Cc, Cv = the effect's curves, i = a frame of the sub-span):
+ *   f_m[i] = (0 + Cm(i)) * (freq_mul * modulator_mul)      (the scalar product rounded once per paint; the `0 +` is zang.zero
+ *                                                           followed by Curve's `+=`; a frame the curve does not paint is +0.0)
+ *   p[i]   = (0 + sin((t_m + 0) * pi * 2)) * modulator_rad;  t_m += f_m[i] * (1 / sample_rate)     (SineOsc.zig:62-75)
+ *   f_c[i] = (0 + Cc(i)) * (freq_mul * carrier_mul)
+ *   c[i]   = 0 + sin((t_c + p[i]) * pi * 2);                 t_c += f_c[i] * (1 / sample_rate)     (SineOsc.zig:76-85)
+ *   out[i] += (0 + Cv(i)) * c[i]                            (multiply, round, add: never fused; on EVERY frame of the sub-span)
+ * and after the sub-span t_m -= trunc(t_m), t_c -= trunc(t_c).
+ * An EFFECT KIT (zh_sfx_kit) holds K effects, each three node lists (any length, 0 too) with their own interpolation function:
+ * all nodes concatenated in one device array beside a descriptor table.  The reference hard-wires one triple and gets its four
+ * sounds from the four scalars (:161-220); here the effect index is a per-note value beside them.  zh_sfx_kit_create is THE ONE
+ * PLACE where zh_sfx_curve.nodes is read as a HOST pointer; it synchronises and is not capturable.  zh_sfx_kit_effect fills a
+ * zh_sfx_effect whose `nodes` are DEVICE pointers (valid while the kit lives): what zh_curve_module_params.curve takes, to paint
+ * an effect stage by stage.  zh_sfx_effect_default fills in the reference's triple (:22-38; nodes[0..2] modulator, [3..5]
+ * carrier, [6..8] volume, all smoothstep).  ZH_ERR_INVALID: n == 0, nodes == NULL with count > 0, a function outside
+ * ZH_CURVE_FN_*; nothing is created then.  Destroy a kit after the last paint that reads it has run, and before its context.
+ * Each curve behaves exactly as zh_curve_module_paint does for the same node list, function, sample rate, note_id_changed and
+ * sub-span length (hostile node times and the at-most-32 span nodes per paint included).  As there, the node carried over from
+ * the previous paint is read at the index that paint left (current_song_note), counted from the first node of the curve the
+ * sub-span plays NOW: when the effect changes without note_id_changed, that is whichever node of the kit's array lies there
+ * (the array ends with as many zero nodes as the kit's longest curve has, so the read stays inside it; an index that only
+ * zh_laser_set_state can produce, past the array, drops the carried node).  An effect index >= the kit's count is DEFINED:
+ * nothing is painted, none of the five states changes, no node is read -- even when note_id_changed is set.
+ * zh_laser_paint_spans is the Trigger loop of :149-158 for every voice in one launch, with the contract of
+ * zh_sampler_paint_kit_spans: empty sub-spans run their prologue, a sub-span out of order ends the voice's list,
+ * ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end), ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; a field without a span
+ * array takes its value from `params` (a broadcast value or a per-voice device array).  Neither paint allocates or
+ * synchronises: both are capturable, and paints, span paints and graph replays of one zh_laser mix.
+ * ZH_ERR_INVALID: what zh_<module>_paint_spans refuses, a NULL kit, a kit of another context, an output image that is NULL or
+ * too small. */
+typedef struct zh_sfx_kit zh_sfx_kit;
+typedef struct zh_sfx_curve { const zh_curve_node *nodes; uint32_t count; uint32_t function; } zh_sfx_curve;   /* function: ZH_CURVE_FN_* */
+typedef struct zh_sfx_effect { zh_sfx_curve modulator, carrier, volume; } zh_sfx_effect;               /* :22-38, in paint order */
+ZH_API int zh_sfx_effect_default(zh_sfx_effect *effect, zh_curve_node *nodes /*[9]: what the effect's curves point at*/);
+ZH_API int zh_sfx_kit_create(zh_ctx *ctx, const zh_sfx_effect *effects, uint32_t n, zh_sfx_kit **out);
+ZH_API int zh_sfx_kit_destroy(zh_sfx_kit *kit);
+ZH_API int zh_sfx_kit_count(const zh_sfx_kit *kit, uint32_t *count_out);
+ZH_API int zh_sfx_kit_effect(const zh_sfx_kit *kit, uint32_t i, zh_sfx_effect *out);
+typedef struct zh_laser zh_laser;
+typedef struct zh_laser_params {                                                                       /* :43-49 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq_mul, carrier_mul, modulator_mul, modulator_rad;
+    zh_u32 effect;         /* index into the kit */
+    const zh_sfx_kit *kit;
+} zh_laser_params;
+typedef struct zh_laser_state {                                                                        /* :51-55 */
+    zh_curve_module_state carrier_curve; zh_sineosc_state carrier;
+    zh_curve_module_state modulator_curve; zh_sineosc_state modulator;
+    zh_curve_module_state volume_curve;
+} zh_laser_state;
+enum { ZH_LASER_SPAN_FREQ_MUL = 0,        /* f */
+       ZH_LASER_SPAN_CARRIER_MUL,         /* f */
+       ZH_LASER_SPAN_MODULATOR_MUL,       /* f */
+       ZH_LASER_SPAN_MODULATOR_RAD,       /* f */
+       ZH_LASER_SPAN_EFFECT,              /* u */
+       ZH_LASER_SPAN_FIELDS };
+ZH_API int zh_laser_create(zh_ctx *ctx, uint32_t n_voices, zh_laser **out);                            /* init() :57-65 */
+ZH_API int zh_laser_destroy(zh_laser *m);
+ZH_API int zh_laser_get_state(zh_laser *m, zh_laser_state *host);
+ZH_API int zh_laser_set_state(zh_laser *m, const zh_laser_state *host);
+ZH_API int zh_laser_paint(zh_laser *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs,
+                          const zh_buf *temps /*[3], unused; may be NULL*/,
+                          zh_bool note_id_changed, const zh_laser_params *params, uint32_t flags);     /* :67-116 */
+ZH_API int zh_laser_paint_spans(zh_laser *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs, const zh_buf *temps,
+                                const zh_laser_params *params, const zh_script_span_param *span_params /*[ZH_LASER_SPAN_FIELDS]*/,
+                                const zh_script_span_table *table, uint32_t flags);                    /* the Trigger loop :149-158 */
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

@@ -357,6 +357,49 @@ public:
     zh_sample sample(uint32_t i) const { zh_sample s{}; check(zh_sample_kit_sample(h_, i, &s), "zh_sample_kit_sample"); return s; }
 };
 
+// K sound effects resident on the device (zh_sfx_kit), each three curves: `effects[i].<curve>.nodes` are HOST pointers here, copied
+// once; effect(i) hands entry i back with DEVICE pointers, for zh_curve_module_paint.  Destroy it before its context.
+class SfxKit {
+    zh_sfx_kit *h_ = nullptr;
+
+public:
+    SfxKit(Context &ctx, const std::vector<zh_sfx_effect> &effects) {
+        check(zh_sfx_kit_create(ctx.get(), effects.data(), (uint32_t)effects.size(), &h_), "zh_sfx_kit_create");
+    }
+    ~SfxKit() { if (h_) zh_sfx_kit_destroy(h_); }
+    SfxKit(const SfxKit &) = delete;
+    SfxKit &operator=(const SfxKit &) = delete;
+    zh_sfx_kit *get() const { return h_; }
+    uint32_t count() const { uint32_t n = 0; check(zh_sfx_kit_count(h_, &n), "zh_sfx_kit_count"); return n; }
+    zh_sfx_effect effect(uint32_t i) const { zh_sfx_effect e{}; check(zh_sfx_kit_effect(h_, i, &e), "zh_sfx_kit_effect"); return e; }
+};
+
+// LaserPlayer (examples/example_laser.zig:40-117) for n voices as one fused kernel; the curves come from an SfxKit
+class Laser {
+    zh_laser *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 1;
+    static constexpr size_t num_temps = 3;
+    using Params = zh_laser_params;
+    using State = zh_laser_state;
+    Laser(Context &ctx, uint32_t n_voices) { check(zh_laser_create(ctx.get(), n_voices, &h_), "zh_laser_create"); }
+    ~Laser() { if (h_) zh_laser_destroy(h_); }
+    Laser(const Laser &) = delete;
+    Laser &operator=(const Laser &) = delete;
+    zh_laser *get() const { return h_; }
+    void getState(State *host) const { check(zh_laser_get_state(h_, host), "zh_laser_get_state"); }
+    void setState(const State *host) { check(zh_laser_set_state(h_, host), "zh_laser_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 1> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_laser_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_laser_paint");
+    }
+    // MainModule's Trigger loop (:149-158) for every voice in one call; span_params = host array [ZH_LASER_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 1> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_laser_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_laser_paint_spans");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

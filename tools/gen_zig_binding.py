@@ -62,6 +62,9 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 *[("zh_%s_paint_spans" % m, "span_params") for m in ("sineosc", "pulseosc", "trisawosc", "noise", "envelope", "gate",
                                                                      "filter", "sampler", "decimator", "distortion")],
                 ("zh_sampler_paint_kit_spans", "span_params"),
+                ("zh_laser_paint_spans", "span_params"),
+                # n effects; the nine nodes of the default effect
+                ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
                 # n samples
                 ("zh_sample_kit_create", "samples"),
                 # the batch call reads n_buffers elements of each

@@ -252,6 +252,27 @@ class FMState(C.Structure):
     _fields_ = [("modulator", FMOpState), ("carrier", FMOpState)]
 
 
+class SfxCurve(C.Structure):               # zh_sfx_curve
+    _fields_ = [("nodes", vp), ("count", u32), ("function", u32)]
+
+
+class SfxEffect(C.Structure):              # zh_sfx_effect
+    _fields_ = [("modulator", SfxCurve), ("carrier", SfxCurve), ("volume", SfxCurve)]
+
+
+class LaserParams(C.Structure):            # zh_laser_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq_mul", F32), ("carrier_mul", F32), ("modulator_mul", F32),
+                ("modulator_rad", F32), ("effect", U32), ("kit", vp)]
+
+
+class LaserState(C.Structure):             # zh_laser_state: the field order of examples/example_laser.zig:51-55
+    _fields_ = [("carrier_curve", CurveModuleState), ("carrier", SineOscState), ("modulator_curve", CurveModuleState),
+                ("modulator", SineOscState), ("volume_curve", CurveModuleState)]
+
+
+LASER_SPAN_FREQ_MUL, LASER_SPAN_CARRIER_MUL, LASER_SPAN_MODULATOR_MUL, LASER_SPAN_MODULATOR_RAD, LASER_SPAN_EFFECT, LASER_SPAN_FIELDS = range(6)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -558,6 +579,17 @@ SIGNATURES = {
     "zh_fm_set_state": (C.c_int, [vp, vp]),
     "zh_fm_paint": (C.c_int, _paint(FMParams)),
     "zh_fm_paint_spans": (C.c_int, [vp, u32, u32, P(Buf), P(Buf), f32, Buf, Buf, P(SpanTable), u32]),
+    "zh_sfx_effect_default": (C.c_int, [P(SfxEffect), P(CurveNode)]),
+    "zh_sfx_kit_create": (C.c_int, [vp, P(SfxEffect), u32, P(vp)]),
+    "zh_sfx_kit_destroy": (C.c_int, [vp]),
+    "zh_sfx_kit_count": (C.c_int, [vp, P(u32)]),
+    "zh_sfx_kit_effect": (C.c_int, [vp, u32, P(SfxEffect)]),
+    "zh_laser_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_laser_destroy": (C.c_int, [vp]),
+    "zh_laser_get_state": (C.c_int, [vp, vp]),
+    "zh_laser_set_state": (C.c_int, [vp, vp]),
+    "zh_laser_paint": (C.c_int, _paint(LaserParams)),
+    "zh_laser_paint_spans": (C.c_int, _paint_spans(LaserParams)),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

@@ -783,3 +783,33 @@ class FMInstrument(_Module):
         rc = self.lib.zh_fm_paint_spans(self.handle, span.start, span.end, _bufarray(outputs), _bufarray(temps), float(sample_rate),
                                         as_buf(tremolo_input), as_buf(vibrato_input), C.byref(table.c), self._flags(zero_first, split))
         abi.check(rc, "zh_fm_paint_spans")
+
+
+class Laser(_Module):
+    """examples/example_laser.zig:40-117: LaserPlayer -- three Curves (modulator frequency, carrier frequency, volume) driving
+    a phase-modulated pair of SineOscs -- as one fused kernel.  The curves come from an effect kit (zang_amd.sfx.SfxKit); the
+    effect index is a per-voice / per-note value beside the four scalars."""
+    _prefix = "laser"
+    _state_ctype = abi.LaserState
+    num_temps = 3
+
+    @dataclass
+    class Params:
+        kit: Any                    # SfxKit
+        sample_rate: float
+        freq_mul: Any = 1.0         # float, or float32 CUDA tensor [n_voices]
+        carrier_mul: Any = 1.0
+        modulator_mul: Any = 1.0
+        modulator_rad: Any = 1.0
+        effect: Any = 0             # int, or int32 CUDA tensor [n_voices]: the index into the kit
+
+    _span_fields = (("freq_mul", "constant"), ("carrier_mul", "constant"), ("modulator_mul", "constant"), ("modulator_rad", "constant"),
+                    ("effect", "tag"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.LaserParams(params.sample_rate, 0, as_f32(params.freq_mul), as_f32(params.carrier_mul), as_f32(params.modulator_mul),
+                               as_f32(params.modulator_rad), as_u32(params.effect), params.kit.handle)
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+        self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
