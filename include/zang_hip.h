@@ -1046,6 +1046,61 @@ ZH_API int zh_laser_paint_spans(zh_laser *m, uint32_t span_start, uint32_t span_
                                 const zh_laser_params *params, const zh_script_span_param *span_params /*[ZH_LASER_SPAN_FIELDS]*/,
                                 const zh_script_span_table *table, uint32_t flags);                    /* the Trigger loop :149-158 */
 
+/* ---------------------------------------------------------------- detuned voice (examples/example_detuned.zig:31-169)
+ * OuterInstrument over Instrument as ONE kernel: a sawtooth whose frequency is warbled by low-passed white noise, enveloped,
+ * then low-passed again.  Bit-identical to the reference's stage order; per frame i of a sub-span (Zig lines on the right):
+ *   n      = 0 + (rand * 2 - 1)                                                  :139-140  white, one draw per frame
+ *   w      = 0 + LP_noise(n; cut = clamp(cutoffFromFrequency(warble_hz, sr)), res 0.0)      :141-150
+ *   if ((mode & 1) == 0) w = w * warble_wide                                     :152-154
+ *   f      = freq * pow(2.0, w)                   (a store, not an add)          :61-65
+ *   o      = 0 + trisaw(t; color);  t += f / sample_rate                         :67-72   TriSawOsc's frequency-buffer path
+ *   out1  += f                                    (skipped when outputs[1].ptr is NULL)     :74
+ *   o      = o * volume                                                          :76
+ *   e      = 0 + env                              (a frame the envelope does not paint keeps the 0)   :78-86
+ *   x      = 0 + o * e                            (multiply, round, add: never fused)       :87-88
+ *   out0  += LP_main(x; cut = clamp(cutoffFromFrequency(cutoff_hz, sr)), res)    :90-99
+ * and after the sub-span t -= trunc(t).  Every `0 +` is zang.zero followed by a module's `+=` (-0.0 becomes +0.0).  Both cutoffs
+ * are computed once per sub-span.  note_id_changed reaches the envelope only: the noise, both filters and the oscillator carry
+ * their state across notes.  The patch holds the reference's constants; every patch value, sample_rate and freq, hostile ones
+ * included, is DEFINED: the voice does what the stage-by-stage composition of the existing paints does with the same value.
+ * zh_detuned_create seeds voice v as zh_noise_create does (first_seed + v).  zh_detuned_state.noise.b is not part of the voice
+ * (white noise never reads the taps): get_state reports zeros, set_state ignores it; osc.cnt is carried untouched.
+ * zh_detuned_paint_spans is the Trigger loop of :213-222 for every voice in one launch, with the contract of
+ * zh_laser_paint_spans: empty sub-spans run their prologue, a sub-span out of order ends the voice's list, ZH_PAINT_ZERO_FIRST
+ * writes all of [span_start, span_end) of BOTH outputs, ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; frames outside every sub-span
+ * touch no state (the noise does not advance there); a field without a span array takes its value from `params` (a broadcast
+ * value or a per-voice device array).  Neither paint allocates or synchronises: both are capturable, and paints, span paints
+ * and graph replays of one zh_detuned mix.  outputs[0] = the voice, outputs[1] = the frequency image (the reference's
+ * oscilloscope sync); an outputs[1] whose ptr is NULL is not painted.
+ * ZH_ERR_INVALID: what zh_laser_paint[_spans] refuses, an outputs[0] that is NULL or too small, an outputs[1] that is not NULL
+ * and too small. */
+typedef struct zh_detuned zh_detuned;
+typedef struct zh_detuned_patch {          /* the reference's constants; uniform over a call */
+    float warble_hz, warble_wide;          /* 4.0, 4.0       :146, :153 */
+    float color, volume;                   /* 0.0, 0.75      :71, :76   */
+    float attack, decay, release, sustain_volume;   /* cubed 0.025, 0.1, 1.0; 0.5   :81-84 */
+    float cutoff_hz, res;                  /* 880.0, 0.8     :95, :98   */
+} zh_detuned_patch;
+typedef struct zh_detuned_params {                                                                     /* :106-111 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on; zh_u32 mode;     /* broadcast or per-voice device arrays; mode bit 0 set = narrow warble */
+    zh_detuned_patch patch;
+} zh_detuned_params;
+typedef struct zh_detuned_state { zh_noise_state noise; zh_filter_state noise_filter; zh_trisawosc_state osc;
+                                  zh_envelope_state env; zh_filter_state main_filter; } zh_detuned_state;   /* :113-115, :41-43 */
+enum { ZH_DETUNED_SPAN_FREQ = 0 /* f */, ZH_DETUNED_SPAN_NOTE_ON /* u */, ZH_DETUNED_SPAN_MODE /* u */, ZH_DETUNED_SPAN_FIELDS };
+ZH_API int zh_detuned_patch_default(zh_detuned_patch *patch);
+ZH_API int zh_detuned_create(zh_ctx *ctx, uint32_t n_voices, uint64_t first_seed, zh_detuned **out);   /* init() :117-123 */
+ZH_API int zh_detuned_destroy(zh_detuned *m);
+ZH_API int zh_detuned_get_state(zh_detuned *m, zh_detuned_state *host);
+ZH_API int zh_detuned_set_state(zh_detuned *m, const zh_detuned_state *host);
+ZH_API int zh_detuned_paint(zh_detuned *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                            const zh_buf *temps /*[4], unused; may be NULL*/,
+                            zh_bool note_id_changed, const zh_detuned_params *params, uint32_t flags); /* :125-168 */
+ZH_API int zh_detuned_paint_spans(zh_detuned *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/, const zh_buf *temps,
+                                  const zh_detuned_params *params, const zh_script_span_param *span_params /*[ZH_DETUNED_SPAN_FIELDS]*/,
+                                  const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :213-222 */
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

@@ -400,6 +400,35 @@ public:
     }
 };
 
+// OuterInstrument over Instrument (examples/example_detuned.zig:31-169) for n voices as one fused kernel: outputs[0] = the voice,
+// outputs[1] = the frequency image (a zh_buf{} whose ptr is NULL: not painted); voice v's noise is seeded with first_seed + v
+class Detuned {
+    zh_detuned *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 4;
+    using Params = zh_detuned_params;
+    using Patch = zh_detuned_patch;
+    using State = zh_detuned_state;
+    Detuned(Context &ctx, uint32_t n_voices, uint64_t first_seed = 0) { check(zh_detuned_create(ctx.get(), n_voices, first_seed, &h_), "zh_detuned_create"); }
+    ~Detuned() { if (h_) zh_detuned_destroy(h_); }
+    Detuned(const Detuned &) = delete;
+    Detuned &operator=(const Detuned &) = delete;
+    zh_detuned *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_detuned_patch_default(&p), "zh_detuned_patch_default"); return p; }
+    void getState(State *host) const { check(zh_detuned_get_state(h_, host), "zh_detuned_get_state"); }
+    void setState(const State *host) { check(zh_detuned_set_state(h_, host), "zh_detuned_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_detuned_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_detuned_paint");
+    }
+    // MainModule's Trigger loop (:213-222) for every voice in one call; span_params = host array [ZH_DETUNED_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_detuned_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_detuned_paint_spans");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -273,6 +273,23 @@ class LaserState(C.Structure):             # zh_laser_state: the field order of 
 LASER_SPAN_FREQ_MUL, LASER_SPAN_CARRIER_MUL, LASER_SPAN_MODULATOR_MUL, LASER_SPAN_MODULATOR_RAD, LASER_SPAN_EFFECT, LASER_SPAN_FIELDS = range(6)
 
 
+class DetunedPatch(C.Structure):           # zh_detuned_patch: the constants of examples/example_detuned.zig
+    _fields_ = [("warble_hz", f32), ("warble_wide", f32), ("color", f32), ("volume", f32), ("attack", f32), ("decay", f32),
+                ("release", f32), ("sustain_volume", f32), ("cutoff_hz", f32), ("res", f32)]
+
+
+class DetunedParams(C.Structure):          # zh_detuned_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool), ("mode", U32), ("patch", DetunedPatch)]
+
+
+class DetunedState(C.Structure):           # zh_detuned_state: the field order of examples/example_detuned.zig:113-115, :41-43
+    _fields_ = [("noise", NoiseState), ("noise_filter", FilterState), ("osc", TriSawOscState), ("env", EnvelopeState),
+                ("main_filter", FilterState)]
+
+
+DETUNED_SPAN_FREQ, DETUNED_SPAN_NOTE_ON, DETUNED_SPAN_MODE, DETUNED_SPAN_FIELDS = range(4)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -590,6 +607,13 @@ SIGNATURES = {
     "zh_laser_set_state": (C.c_int, [vp, vp]),
     "zh_laser_paint": (C.c_int, _paint(LaserParams)),
     "zh_laser_paint_spans": (C.c_int, _paint_spans(LaserParams)),
+    "zh_detuned_patch_default": (C.c_int, [P(DetunedPatch)]),
+    "zh_detuned_create": (C.c_int, [vp, u32, u64, P(vp)]),
+    "zh_detuned_destroy": (C.c_int, [vp]),
+    "zh_detuned_get_state": (C.c_int, [vp, vp]),
+    "zh_detuned_set_state": (C.c_int, [vp, vp]),
+    "zh_detuned_paint": (C.c_int, _paint(DetunedParams)),
+    "zh_detuned_paint_spans": (C.c_int, _paint_spans(DetunedParams)),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

@@ -66,6 +66,7 @@ const FormRow kForms[ZF_COUNT] = {
     /* ZF_GRAPH_DIRECT       */ {"graph_direct", 1, "zh_graph_launch of a ZH_CAPTURE_COALESCE capture that recorded nothing but held-back oscillator batches: 1 = their launches enqueued directly, one per batch of up to 32 buffers (20 paints: one launch of 20), 0 = the recorded hipGraph (20 paints: two launches of 10)"},
     /* ZF_STEREO_ECHOES_PC_MAX */ {"stereo_echoes_pc_max", 32768, "StereoEchoes: up to here loader / filter / writer waves (k_stereo_echoes_pc); StereoEchoes(15000), 1,024 frames, role waves against the walk: 253 / 318 us at 32,768 voices, 518 / 454 at 65,536 (profiles/r10)"},
     /* ZF_LASER_UNIFORM_WALK */ {"laser_uniform_walk", 0, "zh_laser_paint: 0 = its own kernel, no table walk (k_laser); 1 = k_laser_spans over a table of one sub-span per voice (the walk's cost, A/B)"},
+    /* ZF_DETUNED_UNIFORM_WALK */ {"detuned_uniform_walk", 0, "zh_detuned_paint: 0 = its own kernel, no table walk (k_detuned); 1 = k_detuned_spans over a table of one sub-span per voice (the walk's cost, A/B)"},
 };
 
 struct Overrides { bool set[ZF_COUNT]; long val[ZF_COUNT]; };

@@ -813,3 +813,72 @@ class Laser(_Module):
 
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
         self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
+
+
+class Detuned(_Module):
+    """examples/example_detuned.zig:31-169: OuterInstrument over Instrument -- a sawtooth whose frequency is warbled by
+    low-passed white noise, enveloped, then low-passed again -- as one fused kernel.  outputs = [voice image] or [voice image,
+    frequency image] (the reference's oscilloscope sync; None or left out: not painted).  `first_seed`: voice v's noise is
+    seeded like the (first_seed + v)-th Noise.init()."""
+    _prefix = "detuned"
+    _state_ctype = abi.DetunedState
+    num_outputs = 2
+    num_temps = 4
+
+    @dataclass
+    class Patch:                    # the reference's constants (:146, :153, :71, :76, :81-84, :95, :98)
+        warble_hz: float = 4.0
+        warble_wide: float = 4.0
+        color: float = 0.0
+        volume: float = 0.75
+        attack: float = 0.025       # the three curves are cubed
+        decay: float = 0.1
+        release: float = 1.0
+        sustain_volume: float = 0.5
+        cutoff_hz: float = 880.0
+        res: float = 0.8
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        mode: Any = 0               # int, or int32 CUDA tensor [n_voices]: bit 0 set = narrow warble
+        patch: Any = None           # Detuned.Patch; None = the reference's
+
+    _span_fields = (("freq", "constant"), ("note_on", "boolean"), ("mode", "tag"))
+
+    def __init__(self, n_voices, ctx=None, first_seed=0):
+        super().__init__(n_voices, ctx, C.c_uint64(first_seed))
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or Detuned.Patch()
+        patch = abi.DetunedPatch(p.warble_hz, p.warble_wide, p.color, p.volume, p.attack, p.decay, p.release, p.sustain_volume,
+                                 p.cutoff_hz, p.res)
+        return abi.DetunedParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), as_u32(params.mode), patch)
+
+    @staticmethod
+    def _outputs(outputs):
+        """the C side reads outputs[0] and outputs[1]: a missing frequency image is a zh_buf whose ptr is NULL"""
+        outs = list(outputs)
+        arr = (abi.Buf * 2)()
+        arr[0] = as_buf(outs[0])
+        if len(outs) > 1 and outs[1] is not None:
+            arr[1] = as_buf(outs[1])
+        return arr
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+        cp = self._cparams(params)
+        rc = self.lib.zh_detuned_paint(self.handle, span.start, span.end, self._outputs(outputs), None, as_bool(note_id_changed), C.byref(cp),
+                                       abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, "zh_detuned_paint")
+
+    def _paint_spans(self, span, outputs, temps, params, table, flags, span_params=None):
+        cp = self._cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._span_fields])
+        if span_params is not None:
+            sp = span_params
+        rc = self.lib.zh_detuned_paint_spans(self.handle, span.start, span.end, self._outputs(outputs), None, C.byref(cp), sp, C.byref(tb), flags)
+        self._keep = (cp, outputs, table)
+        return rc
