@@ -250,8 +250,19 @@ ZH_API int zh_multiply_with_scalar(zh_ctx *ctx, uint32_t span_start, uint32_t sp
 
 /* Voice mixdown: dst[f] += sum over voices of src[f][v], f in the span -- what V successive
  * zang.addInto calls onto one mix buffer do (basics.zig:31-36; example_song.zig:382-396),
- * summed in a FIXED tree order (wave shuffle -> LDS -> block partials -> second pass) so
- * results are reproducible run to run.  `dst` is a device float[frames]. */
+ * summed in a FIXED order, so a given (voice count, entry point, row form) always gives the same bits.  `dst` is a device
+ * float[frames], added LAST: dst = (ZH_PAINT_ZERO_FIRST ? 0.0f : dst) + total.  The two orders (tests/mix_order_reference.py
+ * restates both in numpy float32, and the GPU suite holds every frame to it bit for bit):
+ *  - zh_mixdown_voices: tiles of 1,024 voices; lane i of 256 adds its quad ((x0 + x1) + x2) + x3 (a quad cut by the voice count:
+ *    0.0f, then += each live voice); a wave's 64 quad sums go through an xor butterfly (32, 16, 8, 4, 2, 1); the four wave sums
+ *    of a tile meet in LDS, ((w0 + w1) + w2) + w3.  Second pass: 16 segments of ceil(tiles / 16) consecutive tiles, each a
+ *    chain from 0.0f in tile order; total = seg0 + seg1 + ... + seg15.
+ *  - zh_nice_paint_mix[_stereo[_batch]]: nothing is shuffled.  Per wave of 64 voices, half h of a frame is the chain x[32h] + x[32h + 1]
+ *    + ... + x[32h + 31] (stereo: of the products x * gain, each rounded to f32, never fused; lanes past the last voice add +0.0);
+ *    the wave's row is h0 + h1; from 65,536 voices (form row nice_mix_wg_min) the four rows of a workgroup meet in LDS,
+ *    ((w0 + w1) + w2) + w3, and one row per 256 voices is written.  Second pass: 128 thread classes, class q a chain from 0.0f
+ *    over rows q, q + 128, ...; total = s0 + s1 + ... + s127; the channels are independent.
+ * Both second passes start at +0.0f, so a sum of -0.0 voices is +0.0. */
 ZH_API int zh_mixdown_voices(zh_ctx *ctx, uint32_t span_start, uint32_t span_end, float *dst, zh_buf src, uint32_t flags);
 /* flags for zh_mixdown_voices: ZH_PAINT_ZERO_FIRST, and ZH_MIX_SEQUENTIAL = add voice 0, 1, 2, ... in
  * that order in f32 exactly like successive `+=` paints onto one buffer (example_song.zig:340-346);

@@ -94,9 +94,11 @@ def test_basics_empty_span_and_errors(ctx):
 @pytest.mark.parametrize("V", [64, 1000, 4096, 5000])
 def test_mixdown_voices(ctx, V):
     """The GPU sums in a fixed tree order; the reference adds voice after voice in f32.
-    Gate against an f64 sum with a sqrt(V)*eps-scaled bound and check
-    run-to-run determinism."""
+    Gate against an f64 sum with a sqrt(V)*eps-scaled bound, check
+    run-to-run determinism, and hold every frame to the tree order itself, bit for bit
+    (tests/mix_order_reference.py; tests/test_gpu_mix_order.py has the edges)."""
     import torch
+    from tests import mix_order_reference as mo
     from zang_amd import zang
     F = 256
     src = util.rng_buffers(9, V, F)
@@ -113,6 +115,7 @@ def test_mixdown_voices(ctx, V):
     bound = 4 * np.sqrt(V) * np.finfo(np.float32).eps * np.abs(src).astype(np.float64).sum(axis=0).max()
     assert np.abs(got - ref).max() <= bound
     assert np.array_equal(got[:3], np.full(3, 0.5, np.float32))
+    util.assert_bitexact(got, mo.tree_mix_span(src, np.full(F, 0.5, np.float32), 3, F, False), f"tree order, {V} voices")
 
 
 @pytest.mark.parametrize("V", [100, 16384])

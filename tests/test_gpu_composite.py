@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import mix_order_reference as mo
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +114,7 @@ def test_nice_paint_mix(ctx, oracle, wg_min, monkeypatch):
     import torch
     from zang_amd import modules as mod, zang, workloads
     V = 1000          # not a multiple of 256: tail lanes
+    rows_per = "workgroup" if wg_min is not None else mo.rows_per_for(V, ctx.forms()["nice_mix_wg_min"][1])
     freq, color, _, _ = workloads.voice_params(5, 7, V)
     m1 = mod.NiceInstrument(V, util.dev(color), ctx)
     m2 = mod.NiceInstrument(V, util.dev(color), ctx)
@@ -131,6 +133,8 @@ def test_nice_paint_mix(ctx, oracle, wg_min, monkeypatch):
         bound = 4 * np.sqrt(V) * np.finfo(np.float32).eps * max(np.abs(pv).sum(axis=1).max(), 1.0)
         assert np.abs(got - ref).max() <= bound
         assert np.array_equal(got[:s], np.full(s, 0.25, np.float32))
+        # ... and the documented summation order, bit for bit in every frame (tests/mix_order_reference.py)
+        util.assert_bitexact(got, mo.fused_mix_span(per_voice.cpu().numpy(), None, np.full(F, 0.25, np.float32), s, e, False, rows_per), f"mono order ({s}, {e})")
     assert np.array_equal(m1.state(), m2.state())
 
 
@@ -139,12 +143,14 @@ def test_nice_paint_mix_stereo(ctx, oracle, wg_min, monkeypatch):
     """Two channels (examples/example_stereo.zig:84-98 with a constant pan per voice): every voice is added to the left
     channel times its left gain and to the right channel times (1 - left); the per-voice products are f32, their sum
     over the voices is checked against the f64 sum with the sqrt(V) * eps bound; with both gains 1.0 the two channels
-    equal the mono mixdown bit for bit (x * 1.0 == x, same summation order)."""
+    equal the mono mixdown bit for bit (x * 1.0 == x, same summation order).  Both channels and the mono mixdown are also held
+    to the documented summation order bit for bit (tests/mix_order_reference.py)."""
     if wg_min is not None:
         util.set_form(monkeypatch, nice_mix_wg_min=wg_min)
     import torch
     from zang_amd import modules as mod, zang, workloads
     V = 1000
+    rows_per = "workgroup" if wg_min is not None else mo.rows_per_for(V, ctx.forms()["nice_mix_wg_min"][1])
     freq, color, u2, _ = workloads.voice_params(5, 7, V)
     pan = (2.0 * u2 - 1.0).astype(np.float32)
     # scaleWave(min 0, max 1) and invertWaveInPlace of the reference, on the per-voice constant (example_stereo.zig:20-39)
@@ -174,6 +180,10 @@ def test_nice_paint_mix_stereo(ctx, oracle, wg_min, monkeypatch):
             bound = 4 * np.sqrt(V) * np.finfo(np.float32).eps * max(np.abs(prod).sum(axis=1).max(), 1.0)
             assert np.abs(got - ref).max() <= bound
             assert np.array_equal(got[:s], np.full(s, base, np.float32)) and np.array_equal(got[e:], np.full(F - e, base, np.float32))
+        # ... and the documented summation order, bit for bit in every frame
+        want = mo.fused_mix_span(pv, (gl, gr), (np.full(F, 0.25, np.float32), np.full(F, -0.5, np.float32)), s, e, False, rows_per)
+        util.assert_bitexact(left.cpu().numpy(), want[0], f"left order ({s}, {e})"); util.assert_bitexact(right.cpu().numpy(), want[1], f"right order ({s}, {e})")
+        util.assert_bitexact(mono.cpu().numpy(), mo.fused_mix_span(pv, None, np.zeros(F, np.float32), s, e, True, rows_per), f"mono order ({s}, {e})")
         assert torch.equal(l1.view(torch.int32), mono.view(torch.int32)) and torch.equal(r1.view(torch.int32), mono.view(torch.int32))
     assert np.array_equal(m1.state(), m2.state()) and np.array_equal(m1.state(), m4.state())
 

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from tests import mix_groups_cases as mg
+from tests import mix_order_reference as mo
 from tests import paint_cases as pc
 from tests import util
 from tests.test_gpu_basics import OPS, _gpu_op, _oracle_op
@@ -178,6 +179,8 @@ def test_mixdown_voices_from_a_view(ctx, geometry, V):
             ref = 0.5 + src.astype(np.float64).sum(axis=0)
             bound = 4 * np.sqrt(V) * np.finfo(np.float32).eps * np.abs(src).astype(np.float64).sum(axis=0).max()
             assert np.abs(got[s:e] - ref[s:e]).max() <= bound
+            # ... and the tree order itself, bit for bit (tests/mix_order_reference.py)
+            util.assert_bitexact(got, mo.tree_mix_span(src, np.full(FRAMES, 0.5, np.float32), s, e, False), f"tree order [{geometry}]")
         g.check_canaries("mixdown")
 
 
@@ -230,7 +233,8 @@ def test_grouped_mixdown_from_a_view(ctx, oracle, geometry, V):
 @pytest.mark.parametrize("geometry", SMALL_GEOMETRIES)
 def test_nice_fused_mixdown_into_rows_at_element_1(ctx, oracle, geometry, V):
     """NiceInstrument.paint_mix / paint_mix_stereo with the mix rows sliced at element 1 and the per-voice arrays from the geometry,
-    against the per-voice paint summed in f64 (the bound of test_nice_paint_mix: 4 * sqrt(V) * eps * the largest sum of magnitudes)"""
+    against the per-voice paint summed in f64 (the bound of test_nice_paint_mix: 4 * sqrt(V) * eps * the largest sum of magnitudes),
+    and against the documented summation order of that paint, bit for bit (tests/mix_order_reference.py)"""
     import torch
     from zang_amd import modules as mod, zang, workloads
     g = _geo(geometry, V)
@@ -239,6 +243,7 @@ def test_nice_fused_mixdown_into_rows_at_element_1(ctx, oracle, geometry, V):
     gl = (0.5 + 0.5 * (2.0 * u2 - 1.0)).astype(np.float32); gr = (1.0 - gl).astype(np.float32)
     gc, gf, dgl, dgr = g.per_voice(color), g.per_voice(freq), g.per_voice(gl), g.per_voice(gr)
     m1, m2, m3 = (mod.NiceInstrument(V, gc, ctx) for _ in range(3))
+    rows_per = mo.rows_per_for(V, ctx.forms()["nice_mix_wg_min"][1])
     for k, (on, nic) in enumerate(((True, True), (False, False))):
         per_voice = g.image("out", fill=0.0)
         P = m1.Params(SR, gf, on)
@@ -256,6 +261,10 @@ def test_nice_fused_mixdown_into_rows_at_element_1(ctx, oracle, geometry, V):
             bound = 4 * np.sqrt(V) * np.finfo(np.float32).eps * max(np.abs(terms).sum(axis=1).max(), 1.0)
             assert np.abs(got[r, 1 + s:1 + e] - ref[s:e]).max() <= bound, (k, r)
             assert (got[r, :1 + s] == 0.25).all() and (got[r, 1 + e:] == 0.25).all(), (k, r)
+        quarter = np.full(FRAMES, 0.25, np.float32)                    # ... and the summation order itself, every frame
+        util.assert_bitexact(got[0, 1:1 + FRAMES], mo.fused_mix_span(per_voice.cpu().numpy(), None, quarter, s, e, False, rows_per), f"mono order, paint {k}")
+        for r, want in zip((1, 2), mo.fused_mix_span(per_voice.cpu().numpy(), (gl, gr), (quarter, quarter), s, e, False, rows_per)):
+            util.assert_bitexact(got[r, 1:1 + FRAMES], want, f"stereo order, paint {k} channel {r - 1}")
         assert float(np.abs(pv).max()) > 0.01 or k == 1
         g.check_canaries("nice mix")
         g.release([per_voice])
