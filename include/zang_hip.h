@@ -1112,6 +1112,99 @@ ZH_API int zh_detuned_paint_spans(zh_detuned *m, uint32_t span_start, uint32_t s
                                   const zh_detuned_params *params, const zh_script_span_param *span_params /*[ZH_DETUNED_SPAN_FIELDS]*/,
                                   const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :213-222 */
 
+/* ---------------------------------------------------------------- the monophonic leads: glide and vibrato voices
+ * The two lead instruments of the reference's examples, each as ONE kernel.  They share one Params record (sample_rate, freq,
+ * note_on) and both paint two outputs: outputs[0] = the voice, outputs[1] = the frequency image (the reference's oscilloscope
+ * sync); an outputs[1] whose ptr is NULL is not painted.  Bit-identical to the reference's stage order; every `0 +` below is
+ * zang.zero followed by a module's `+=` (-0.0 becomes +0.0), and no multiply is contracted with an add.
+ *
+ * zh_porta: examples/example_portamento.zig Instrument :20-87.  A sub-span with note_id_changed, freq and note_on begins with
+ *   porta.begin(sample_rate, glide_curve, glide, goal = freq, note_on, prev_note_on, note_id_changed)    :55-61
+ *   env.begin(note_id_changed = !prev_note_on && note_on), cubed attack / decay / release, sustain_volume :65-73
+ *   osc.begin(sample_rate)                          SineOsc's frequency-buffer path, phase constant 0.0  :76-80
+ * then per frame i (Zig lines on the right):
+ *   g      = 0 + porta                              the glide toward freq, or freq itself once arrived   :53-61
+ *   e      = 0 + env                                (a frame the envelope does not paint keeps the 0)    :63-73
+ *   s      = 0 + sin((t + 0.0) * 2 pi);  t += g / sample_rate                                            :75-80
+ *   out0  += e * s                                  (multiply, round, add: never fused)                  :82
+ *   out1  += g                                      (skipped when outputs[1].ptr is NULL)                :85
+ * and after the sub-span t -= trunc(t), then prev_note_on = note_on (the `defer` of :51; an empty sub-span runs it too).
+ * prev_note_on is the note-level bit the voice carries across sub-spans and buffers: the glide is instantaneous unless
+ * note_on && prev_note_on, and the envelope restarts only when every key was up.  The Trigger's note_id_changed reaches the
+ * portamento alone (:55).
+ *
+ * zh_vibrato: examples/example_vibrato.zig Instrument :17-69.  A sub-span begins with vib.begin(sample_rate, vib_hz) and
+ * osc.begin(sample_rate, color); per frame i:
+ *   m      = 0 + sin((tv + 0.0) * 2 pi);  tv += vib_hz / sample_rate                                     :46-51
+ *   f      = freq * (1.0 + depth * m)               (three roundings; a store, not an add)               :52-55
+ *   out1  += f                                      (skipped when outputs[1].ptr is NULL)                :56
+ *   o      = 0 + pulse(cnt; f, color)               PulseOsc's frequency-buffer path: an f below 0 or above sample_rate / 8
+ *                                                   paints nothing, o stays 0 and cnt does not move      :57-62
+ *   k      = 0 + (note_on ? 1.0 : nothing)          Gate                                                 :63-66
+ *   out0  += o * k                                                                                       :67
+ * and after the sub-span tv -= trunc(tv).  note_id_changed reaches no module of this voice: the interface takes it and ignores it.
+ *
+ * For both: inside a sub-span EVERY frame of out0 and out1 is added to, also when the addend is +-0.0 (a -0.0 already in the image
+ * becomes +0.0) and when the PulseOsc paints nothing; frames outside every sub-span touch neither image nor state.  The patches
+ * hold the reference's constants; every patch value, sample_rate and freq, hostile ones included, is DEFINED: the voice does what
+ * the stage-by-stage composition of the existing paints does with the same value.  zh_X_create starts every voice as init() does
+ * (all words zero).
+ * zh_X_paint_spans is the Trigger loop (portamento :119-128, vibrato :101-110) for every voice in one launch, with the contract of
+ * zh_detuned_paint_spans: empty sub-spans run their prologue and epilogue, a sub-span out of order ends the voice's list,
+ * ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end) of BOTH outputs, ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; a field
+ * without a span array takes its value from `params` (a broadcast value or a per-voice device array).  Neither paint allocates
+ * or synchronises: both are capturable, and paints, span paints and graph replays of one object mix.
+ * ZH_ERR_INVALID: what zh_detuned_paint[_spans] refuses, an outputs[0] that is NULL or too small, an outputs[1] that is not NULL
+ * and too small. */
+typedef struct zh_porta zh_porta;
+typedef struct zh_porta_patch {            /* the reference's constants; uniform over a call */
+    uint32_t glide_curve;                  /* ZH_CURVE_*; ZH_CURVE_CUBED   :57 */
+    float glide;                           /* 0.5                          :57 */
+    float attack, decay, release, sustain_volume;   /* cubed 0.025, 0.1, 1.0; 0.5   :68-71 */
+} zh_porta_patch;
+typedef struct zh_porta_params {                                                                       /* :23-27 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on;          /* broadcast or per-voice device arrays */
+    zh_porta_patch patch;
+} zh_porta_params;
+typedef struct zh_porta_state { zh_portamento_state porta; zh_envelope_state env; zh_sineosc_state osc;
+                                uint32_t prev_note_on; } zh_porta_state;                               /* :29-32 */
+enum { ZH_PORTA_SPAN_FREQ = 0 /* f */, ZH_PORTA_SPAN_NOTE_ON /* u */, ZH_PORTA_SPAN_FIELDS };
+ZH_API int zh_porta_patch_default(zh_porta_patch *patch);
+ZH_API int zh_porta_create(zh_ctx *ctx, uint32_t n_voices, zh_porta **out);                            /* init() :34-41 */
+ZH_API int zh_porta_destroy(zh_porta *m);
+ZH_API int zh_porta_get_state(zh_porta *m, zh_porta_state *host);
+ZH_API int zh_porta_set_state(zh_porta *m, const zh_porta_state *host);
+ZH_API int zh_porta_paint(zh_porta *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                          const zh_buf *temps /*[3], unused; may be NULL*/,
+                          zh_bool note_id_changed, const zh_porta_params *params, uint32_t flags);     /* :43-86 */
+ZH_API int zh_porta_paint_spans(zh_porta *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/, const zh_buf *temps,
+                                const zh_porta_params *params, const zh_script_span_param *span_params /*[ZH_PORTA_SPAN_FIELDS]*/,
+                                const zh_script_span_table *table, uint32_t flags);                    /* the Trigger loop :119-128 */
+
+typedef struct zh_vibrato zh_vibrato;
+typedef struct zh_vibrato_patch {          /* the reference's constants; uniform over a call */
+    float vib_hz, depth, color;            /* 4.0, 0.02, 0.5   :49, :54, :61 */
+} zh_vibrato_patch;
+typedef struct zh_vibrato_params {                                                                     /* :20-24 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on;          /* broadcast or per-voice device arrays */
+    zh_vibrato_patch patch;
+} zh_vibrato_params;
+typedef struct zh_vibrato_state { zh_sineosc_state vib; zh_pulseosc_state osc; } zh_vibrato_state;     /* :26-28 (the Gate has no state) */
+enum { ZH_VIBRATO_SPAN_FREQ = 0 /* f */, ZH_VIBRATO_SPAN_NOTE_ON /* u */, ZH_VIBRATO_SPAN_FIELDS };
+ZH_API int zh_vibrato_patch_default(zh_vibrato_patch *patch);
+ZH_API int zh_vibrato_create(zh_ctx *ctx, uint32_t n_voices, zh_vibrato **out);                        /* init() :30-36 */
+ZH_API int zh_vibrato_destroy(zh_vibrato *m);
+ZH_API int zh_vibrato_get_state(zh_vibrato *m, zh_vibrato_state *host);
+ZH_API int zh_vibrato_set_state(zh_vibrato *m, const zh_vibrato_state *host);
+ZH_API int zh_vibrato_paint(zh_vibrato *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                            const zh_buf *temps /*[3], unused; may be NULL*/,
+                            zh_bool note_id_changed, const zh_vibrato_params *params, uint32_t flags); /* :38-68 */
+ZH_API int zh_vibrato_paint_spans(zh_vibrato *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/, const zh_buf *temps,
+                                  const zh_vibrato_params *params, const zh_script_span_param *span_params /*[ZH_VIBRATO_SPAN_FIELDS]*/,
+                                  const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :101-110 */
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

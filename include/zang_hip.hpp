@@ -429,6 +429,65 @@ public:
     }
 };
 
+// Instrument of examples/example_portamento.zig (:20-87) for n voices as one fused kernel: a sine whose frequency glides toward
+// the note's, times an envelope; the voice carries prev_note_on across sub-spans.  outputs[0] = the voice, outputs[1] = the
+// frequency image (a zh_buf{} whose ptr is NULL: not painted)
+class Porta {
+    zh_porta *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 3;
+    using Params = zh_porta_params;
+    using Patch = zh_porta_patch;
+    using State = zh_porta_state;
+    Porta(Context &ctx, uint32_t n_voices) { check(zh_porta_create(ctx.get(), n_voices, &h_), "zh_porta_create"); }
+    ~Porta() { if (h_) zh_porta_destroy(h_); }
+    Porta(const Porta &) = delete;
+    Porta &operator=(const Porta &) = delete;
+    zh_porta *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_porta_patch_default(&p), "zh_porta_patch_default"); return p; }
+    void getState(State *host) const { check(zh_porta_get_state(h_, host), "zh_porta_get_state"); }
+    void setState(const State *host) { check(zh_porta_set_state(h_, host), "zh_porta_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_porta_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_porta_paint");
+    }
+    // MainModule's Trigger loop (:119-128) for every voice in one call; span_params = host array [ZH_PORTA_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_porta_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_porta_paint_spans");
+    }
+};
+
+// Instrument of examples/example_vibrato.zig (:17-69) for n voices as one fused kernel: a pulse whose frequency a slow sine
+// modulates, times a gate.  Outputs as Porta's
+class Vibrato {
+    zh_vibrato *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 3;
+    using Params = zh_vibrato_params;
+    using Patch = zh_vibrato_patch;
+    using State = zh_vibrato_state;
+    Vibrato(Context &ctx, uint32_t n_voices) { check(zh_vibrato_create(ctx.get(), n_voices, &h_), "zh_vibrato_create"); }
+    ~Vibrato() { if (h_) zh_vibrato_destroy(h_); }
+    Vibrato(const Vibrato &) = delete;
+    Vibrato &operator=(const Vibrato &) = delete;
+    zh_vibrato *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_vibrato_patch_default(&p), "zh_vibrato_patch_default"); return p; }
+    void getState(State *host) const { check(zh_vibrato_get_state(h_, host), "zh_vibrato_get_state"); }
+    void setState(const State *host) { check(zh_vibrato_set_state(h_, host), "zh_vibrato_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_vibrato_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_vibrato_paint");
+    }
+    // MainModule's Trigger loop (:101-110) for every voice in one call; span_params = host array [ZH_VIBRATO_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_vibrato_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_vibrato_paint_spans");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -64,6 +64,7 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 ("zh_sampler_paint_kit_spans", "span_params"),
                 ("zh_laser_paint_spans", "span_params"),
                 ("zh_detuned_paint_spans", "span_params"),
+                ("zh_porta_paint_spans", "span_params"), ("zh_vibrato_paint_spans", "span_params"),
                 # n effects; the nine nodes of the default effect
                 ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
                 # n samples

@@ -290,6 +290,36 @@ class DetunedState(C.Structure):           # zh_detuned_state: the field order o
 DETUNED_SPAN_FREQ, DETUNED_SPAN_NOTE_ON, DETUNED_SPAN_MODE, DETUNED_SPAN_FIELDS = range(4)
 
 
+class PortaPatch(C.Structure):             # zh_porta_patch: the constants of examples/example_portamento.zig
+    _fields_ = [("glide_curve", u32), ("glide", f32), ("attack", f32), ("decay", f32), ("release", f32), ("sustain_volume", f32)]
+
+
+class PortaParams(C.Structure):            # zh_porta_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool), ("patch", PortaPatch)]
+
+
+class PortaState(C.Structure):             # zh_porta_state: the field order of examples/example_portamento.zig:29-32
+    _fields_ = [("porta", PortamentoState), ("env", EnvelopeState), ("osc", SineOscState), ("prev_note_on", u32)]
+
+
+PORTA_SPAN_FREQ, PORTA_SPAN_NOTE_ON, PORTA_SPAN_FIELDS = range(3)
+
+
+class VibratoPatch(C.Structure):           # zh_vibrato_patch: the constants of examples/example_vibrato.zig
+    _fields_ = [("vib_hz", f32), ("depth", f32), ("color", f32)]
+
+
+class VibratoParams(C.Structure):          # zh_vibrato_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool), ("patch", VibratoPatch)]
+
+
+class VibratoState(C.Structure):           # zh_vibrato_state: the field order of examples/example_vibrato.zig:26-28
+    _fields_ = [("vib", SineOscState), ("osc", PulseOscState)]
+
+
+VIBRATO_SPAN_FREQ, VIBRATO_SPAN_NOTE_ON, VIBRATO_SPAN_FIELDS = range(3)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -614,6 +644,20 @@ SIGNATURES = {
     "zh_detuned_set_state": (C.c_int, [vp, vp]),
     "zh_detuned_paint": (C.c_int, _paint(DetunedParams)),
     "zh_detuned_paint_spans": (C.c_int, _paint_spans(DetunedParams)),
+    "zh_porta_patch_default": (C.c_int, [P(PortaPatch)]),
+    "zh_porta_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_porta_destroy": (C.c_int, [vp]),
+    "zh_porta_get_state": (C.c_int, [vp, vp]),
+    "zh_porta_set_state": (C.c_int, [vp, vp]),
+    "zh_porta_paint": (C.c_int, _paint(PortaParams)),
+    "zh_porta_paint_spans": (C.c_int, _paint_spans(PortaParams)),
+    "zh_vibrato_patch_default": (C.c_int, [P(VibratoPatch)]),
+    "zh_vibrato_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_vibrato_destroy": (C.c_int, [vp]),
+    "zh_vibrato_get_state": (C.c_int, [vp, vp]),
+    "zh_vibrato_set_state": (C.c_int, [vp, vp]),
+    "zh_vibrato_paint": (C.c_int, _paint(VibratoParams)),
+    "zh_vibrato_paint_spans": (C.c_int, _paint_spans(VibratoParams)),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

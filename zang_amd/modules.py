@@ -882,3 +882,93 @@ class Detuned(_Module):
         rc = self.lib.zh_detuned_paint_spans(self.handle, span.start, span.end, self._outputs(outputs), None, C.byref(cp), sp, C.byref(tb), flags)
         self._keep = (cp, outputs, table)
         return rc
+
+
+class _Lead(_Module):
+    """What the two monophonic leads share: one Params record (sample_rate, freq, note_on, the patch), outputs = [voice image]
+    or [voice image, frequency image] (the reference's oscilloscope sync; None or left out: not painted)."""
+    num_outputs = 2
+    num_temps = 3
+    _span_fields = (("freq", "constant"), ("note_on", "boolean"))
+
+    @staticmethod
+    def _outputs(outputs):
+        """the C side reads outputs[0] and outputs[1]: a missing frequency image is a zh_buf whose ptr is NULL"""
+        outs = list(outputs)
+        arr = (abi.Buf * 2)()
+        arr[0] = as_buf(outs[0])
+        if len(outs) > 1 and outs[1] is not None:
+            arr[1] = as_buf(outs[1])
+        return arr
+
+    def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
+        cp = self._cparams(params)
+        fn = getattr(self.lib, f"zh_{self._prefix}_paint")
+        rc = fn(self.handle, span.start, span.end, self._outputs(outputs), None, as_bool(note_id_changed), C.byref(cp),
+                abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, f"zh_{self._prefix}_paint")
+
+    def _paint_spans(self, span, outputs, temps, params, table, flags, span_params=None):
+        cp = self._cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._span_fields])
+        if span_params is not None:
+            sp = span_params
+        fn = getattr(self.lib, f"zh_{self._prefix}_paint_spans")
+        rc = fn(self.handle, span.start, span.end, self._outputs(outputs), None, C.byref(cp), sp, C.byref(tb), flags)
+        self._keep = (cp, outputs, table)
+        return rc
+
+
+class Porta(_Lead):
+    """examples/example_portamento.zig:20-87: a sine whose frequency glides toward the note's (Portamento), scaled by an Envelope,
+    as one fused kernel.  The voice carries prev_note_on across sub-spans and buffers: the glide is instantaneous and the
+    envelope restarts only when no note was on before."""
+    _prefix = "porta"
+    _state_ctype = abi.PortaState
+
+    @dataclass
+    class Patch:                    # the reference's constants (:57, :68-71)
+        glide_curve: int = abi.CURVE_CUBED
+        glide: float = 0.5
+        attack: float = 0.025       # the three curves are cubed
+        decay: float = 0.1
+        release: float = 1.0
+        sustain_volume: float = 0.5
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        patch: Any = None           # Porta.Patch; None = the reference's
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or Porta.Patch()
+        patch = abi.PortaPatch(int(p.glide_curve), p.glide, p.attack, p.decay, p.release, p.sustain_volume)
+        return abi.PortaParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), patch)
+
+
+class Vibrato(_Lead):
+    """examples/example_vibrato.zig:17-69: a pulse whose frequency a slow sine modulates, scaled by a Gate, as one fused kernel.
+    note_id_changed reaches no module of this voice."""
+    _prefix = "vibrato"
+    _state_ctype = abi.VibratoState
+
+    @dataclass
+    class Patch:                    # the reference's constants (:49, :54, :61)
+        vib_hz: float = 4.0
+        depth: float = 0.02
+        color: float = 0.5
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        patch: Any = None           # Vibrato.Patch; None = the reference's
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or Vibrato.Patch()
+        return abi.VibratoParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), abi.VibratoPatch(p.vib_hz, p.depth, p.color))
