@@ -25,6 +25,11 @@ The table (offsets in floats from a 16-byte-aligned row start; V = voices):
 
 (With off 5 and stride V+8 three floats lie right of a row and five left of the next: the eight floats between two rows of a view
 are all guards, and all are checked.)
+
+A case paints ONE span twice (ZERO_FIRST, then adding) -- or, with `Geometry(..., spans=[...])`, consecutive spans once each with one
+module (the first with ZERO_FIRST, the rest adding onto a zeroed image): `Shared.steps()` walks either plan, for the GPU paints and for
+the oracle's.  tests/test_gpu_span_lengths.py uses the second to hand state from one kernel form to the next.  The cases that do not
+go through `steps()` (Sampler, PMOscInstrument, Curve, Portamento, the stateless ones) refuse a geometry with `spans`.
 """
 import ctypes as C
 
@@ -66,9 +71,16 @@ def _torch():
 class Geometry:
     """Where the images and per-voice arrays of a test lie: see the module's docstring."""
 
-    def __init__(self, name, V, frames=1024, span=None, delay_samples=300, device="cuda"):
+    def __init__(self, name, V, frames=1024, span=None, delay_samples=300, device="cuda", spans=None):
         assert name in GEOMETRIES, name
         self.name, self.V, self.frames, self.device = name, V, frames, device
+        # `spans`: consecutive spans a carried case paints one after the other (the first with ZERO_FIRST, the rest adding)
+        # instead of painting ONE span twice; `span` is then their hull, the rows a paint may write
+        self.spans = None if spans is None else [tuple(sp) for sp in spans]
+        if self.spans is not None:
+            assert span is None and name != "in_place" and len(self.spans) >= 1
+            assert all(a[1] == b[0] for a, b in zip(self.spans, self.spans[1:])), "the spans follow each other"
+            span = (self.spans[0][0], self.spans[-1][1])
         self.span = (0, frames) if span is None else tuple(span)
         self.delay_samples = delay_samples
         self.pv_offset = 1 if name == "params_shifted" else 0
@@ -230,6 +242,8 @@ class Shared:
         return np.ascontiguousarray(img[:, self.tidx].cpu().numpy().T)
 
     def out(self, fill=None):
+        if fill is None and self.geo.spans is not None:
+            fill = 0.0                      # consecutive spans: all but the first ADD, onto the zeros the oracle's image starts from
         o = self.geo.image("out", fill=fill)
         self.outs.append(o)
         return o
@@ -244,8 +258,29 @@ class Shared:
             return Target(o, o, cols.copy(), cols, True)
         return Target(self.out(), image, np.zeros((n, self.F), np.float32), cols, False)
 
+    def steps(self, zf_seq=None):
+        """The carried paints of a case, in order: yields (k, zero_first) with self.s / self.e set to the k-th paint's span.  One
+        span (the default): the span painted once per entry of `zf_seq` (self.zf_seq if None).  A geometry with `spans`: one
+        paint per span, the first with the first entry of `zf_seq`, the rest adding.  Afterwards self.s / self.e are the hull."""
+        seq = self.zf_seq if zf_seq is None else tuple(zf_seq)
+        spans = self.geo.spans
+        plan = [(self.geo.span, zf) for zf in seq] if spans is None else [(sp, seq[0] if k == 0 else False) for k, sp in enumerate(spans)]
+        try:
+            for k, ((s, e), zf) in enumerate(plan):
+                self.s, self.e = s, e
+                yield k, zf
+        finally:
+            self.s, self.e = self.geo.span
+
+    def pieces(self, zf_seq=None):
+        """steps() as a list of (s, e, zero_first): what ref_decimator / ref_filter take as their zf_seq"""
+        return [(self.s, self.e, zf) for _, zf in self.steps(zf_seq)]
+
+    def one_span(self):
+        assert self.geo.spans is None, "this case paints one span twice: it has no form for consecutive spans"
+
     def paints(self, paint):
-        for k, zf in enumerate(self.zf_seq):
+        for k, zf in self.steps():
             paint(k, zf)
 
     def oracle_zero(self, L, oracle, t, j, zf):
@@ -278,6 +313,41 @@ def _crafted_noise_state(k_frames, seed):
     return _xoshiro_step_back([0, int(rng.integers(1, 1 << 63)), int(rng.integers(1, 1 << 63)), 1 << 41], k_frames)
 
 
+def noise_draws(sh, which):
+    """Where the crafted multi-draw samples of case_noise (`which` = "noise": three voices) and case_noise_filter ("filter": two)
+    fall, as draws counted from the first painted frame -- a function of the painted lengths, asserted from the positions
+    themselves:
+     - one span of n frames painted twice (draws [0, n) and [n, 2 n)): from n = 1 on one falls inside the first paint and one
+       inside the second; from n = 128 on one of the first paint's lies past ceil(n / 2) rounded up to 32 frames -- past the first
+       frame range however the span is split in two or more, so that k_noise_fix must repaint the voice -- and from n = 2,048 on
+       past frame 1,024.  At 1,024 frames: 77, n - 23, n + n // 2 + 3, and 300, n + 9;
+     - consecutive spans: one inside the first, one past the first range of the second, one in the later half of the last."""
+    spans = sh.geo.spans
+    if spans is not None:
+        base = spans[0][0]
+        s1, e1 = spans[min(1, len(spans) - 1)]
+        sl, el = spans[-1]
+        first, mid, late = min(77, (spans[0][1] - base) // 2), s1 - base + (e1 - s1) * 7 // 8, sl - base + (el - sl) * 3 // 4
+        assert 0 <= first < max(spans[0][1] - base, 1) and first <= mid <= late < max(el - base, 1), (first, mid, late)
+        return (first, mid, late) if which == "noise" else (mid, late)
+    n = sh.geo.span[1] - sh.geo.span[0]
+    if which == "noise":
+        pos = (min(77, n // 2), max(n - 23, n // 2), max(n + min(n // 2 + 3, n - 1), 0))
+        in_first, in_second = pos[:2], pos[2:]
+    else:
+        pos = (min(300, max(n - 21, n // 2)), max(n + min(9, n - 1), 0))
+        in_first, in_second = pos[:1], pos[1:]
+    if n >= 1:
+        assert all(0 <= q < n for q in in_first) and all(n <= q < 2 * n for q in in_second), (n, pos)
+    if n >= 128 and which == "noise":
+        assert pos[1] >= ((n + 1) // 2 + 31) // 32 * 32, (n, pos)          # past the first of two or more ranges of 32 k frames
+    if n >= 2048 and which == "noise":
+        assert pos[1] > 1024, (n, pos)
+    if n == 1024:
+        assert pos == ((77, n - 23, n + n // 2 + 3) if which == "noise" else (300, n + 9)), pos
+    return pos
+
+
 # ---------------------------------------------------------------------------------------------- the cases
 # each: case(ctx, oracle, sh) -> None; paints on the GPU, runs the oracle for sh.idx, asserts bit-exact images and states
 
@@ -307,7 +377,7 @@ def case_sineosc(ctx, oracle, sh, image):
     ref = t.ref; rt = []
     for j, v in enumerate(sh.idx):
         st = oracle.SineOsc(); L.zo_sineosc_init(C.byref(st))
-        for zf in sh.zf_seq:
+        for _, zf in sh.steps():
             sh.oracle_zero(L, oracle, t, j, zf)
             L.zo_sineosc_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), SR, oracle.buffer(t.col(j)) if image else oracle.constant(sh.freq[v]), oracle.constant(ph))
         rt.append(st.t)
@@ -326,7 +396,7 @@ def case_osc(ctx, oracle, sh, which, image):
     ref = t.ref; rs = []
     for j, v in enumerate(sh.idx):
         st = ocls(); init(C.byref(st))
-        for zf in sh.zf_seq:
+        for _, zf in sh.steps():
             sh.oracle_zero(L, oracle, t, j, zf)
             paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), SR, oracle.buffer(t.col(j)) if image else oracle.constant(sh.freq[v]), float(sh.color[v]))
         rs.append((st.cnt, st.t if which == "trisaw" else 0.0))
@@ -342,6 +412,7 @@ def case_osc(ctx, oracle, sh, which, image):
 def case_sampler(ctx, oracle, sh):
     from zang_amd import modules as mod
     L = oracle.lib()
+    sh.one_span()
     m = mod.Sampler(sh.V, ctx); o = sh.out()
     smp = m.Sample(1, 44100, m.signed16_lsb, sh.gpcm)
     rate = (sh.freq * np.float32(40.0)).astype(np.float32)
@@ -366,16 +437,19 @@ def case_envelope(ctx, oracle, sh):
     from zang_amd import modules as mod, zang
     L = oracle.lib()
     m = mod.Envelope(sh.V, ctx); o = sh.out()
-    on1 = (np.arange(sh.V) % 5 != 0)                     # second buffer: most voices stay on (decay -> sustain), every fifth releases
+    # one span: the second buffer keeps most voices on (decay -> sustain), every fifth releases.  Consecutive spans: a new note
+    # at the first, on through the first four, every voice released from the fifth
+    on1 = (np.arange(sh.V) % 5 != 0) if sh.geo.spans is None else np.zeros(sh.V, bool)
+    off_at = 1 if sh.geo.spans is None else 4
     g_on1 = sh.pv(on1.astype(np.uint8))
     P = lambda on: m.Params(SR, zang.PaintCurve.cubed(0.004), zang.PaintCurve.cubed(0.02), zang.PaintCurve.cubed(0.03), 0.6, on)
-    m.paint(sh.span(), [o], [], True, P(True), zero_first=True)
-    m.paint(sh.span(), [o], [], False, P(g_on1))
+    for k, zf in sh.steps((True, False)):
+        m.paint(sh.span(), [o], [], k == 0, P(True if k < off_at else g_on1), zero_first=zf)
     ref = np.zeros((len(sh.idx), sh.F), np.float32); rs = []
     for j, v in enumerate(sh.idx):
         st = oracle.Envelope(); L.zo_envelope_init(C.byref(st))
-        L.zo_envelope_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), 1, C.byref(_env_params(oracle, True)))
-        L.zo_envelope_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), 0, C.byref(_env_params(oracle, on1[v])))
+        for k, _ in sh.steps((True, False)):
+            L.zo_envelope_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), int(k == 0), C.byref(_env_params(oracle, True if k < off_at else on1[v])))
         rs.append((st.state, st.painter.t, st.painter.last_value, st.painter.start))
     def states():
         gs = m.state()
@@ -385,10 +459,12 @@ def case_envelope(ctx, oracle, sh):
 
 def ref_decimator(oracle, s, e, zf_seq, ref, col, fake, in_place):
     """The oracle's carried Decimator paints of ONE voice onto ref (a [frames] row): -> its state.  in_place: the input IS ref,
-    and ZERO_FIRST is what the reference's caller does -- zang.zero(span, out), then the paint with the same slice twice."""
+    and ZERO_FIRST is what the reference's caller does -- zang.zero(span, out), then the paint with the same slice twice.  An
+    entry of zf_seq is zero_first, or (s, e, zero_first) for a paint with a span of its own (Shared.pieces)."""
     L = oracle.lib()
     st = oracle.Decimator(); L.zo_decimator_init(C.byref(st))
     for zf in zf_seq:
+        s, e, zf = zf if isinstance(zf, tuple) else (s, e, zf)
         if zf:
             L.zo_zero(s, e, oracle.fptr(ref))
         L.zo_decimator_paint(C.byref(st), s, e, oracle.fptr(ref), SR, oracle.fptr(ref if in_place else col), float(fake))
@@ -403,8 +479,9 @@ def case_decimator(ctx, oracle, sh):
     gfake = sh.pv(fake)
     sh.paints(lambda k, zf: m.paint(sh.span(), [t.o], [], False, m.Params(SR, t.src, gfake), zero_first=zf))
     ref = t.ref; rs = []
+    pieces = sh.pieces()
     for j, v in enumerate(sh.idx):
-        st = ref_decimator(oracle, sh.s, sh.e, sh.zf_seq, ref[j], sh.icol[j], fake[v], t.in_place)
+        st = ref_decimator(oracle, sh.s, sh.e, pieces, ref[j], sh.icol[j], fake[v], t.in_place)
         rs.append((st.dval, st.dcount))
     def states():
         gs = m.state()
@@ -418,6 +495,7 @@ def ref_filter(oracle, s, e, zf_seq, ref, col, ftype, cutoff, res, in_place, cut
     L = oracle.lib()
     st = oracle.Filter(); L.zo_filter_init(C.byref(st))
     for zf in zf_seq:
+        s, e, zf = zf if isinstance(zf, tuple) else (s, e, zf)          # (an entry with a span of its own: Shared.pieces)
         if zf:
             L.zo_zero(s, e, oracle.fptr(ref))
         cut = oracle.buffer(ref) if cutoff_in_place else (oracle.buffer(cutoff) if isinstance(cutoff, np.ndarray) else oracle.constant(cutoff))
@@ -434,8 +512,9 @@ def case_filter(ctx, oracle, sh, ftype, cutoff_image):
     cut = zang.buffer(t.src if ctl else sh.cbuf) if cutoff_image else zang.constant(sh.gc)
     sh.paints(lambda k, zf: m.paint(sh.span(), [t.o], [], False, m.Params(src, ftype, cut, zang.constant(0.4)), zero_first=zf))
     ref = t.ref; rs = []
+    pieces = sh.pieces()
     for j, v in enumerate(sh.idx):
-        st = ref_filter(oracle, sh.s, sh.e, sh.zf_seq, ref[j], sh.icol[j], ftype, sh.ccol[j] if cutoff_image else float(sh.color[v]), 0.4,
+        st = ref_filter(oracle, sh.s, sh.e, pieces, ref[j], sh.icol[j], ftype, sh.ccol[j] if cutoff_image else float(sh.color[v]), 0.4,
                         t.in_place and not ctl, bool(ctl))
         rs.append((st.l, st.b))
     def states():
@@ -461,7 +540,7 @@ def case_echoes(ctx, oracle, sh, filtered):
     for j in range(n):
         d = oracle.Delay(); L.zo_delay_init(C.byref(d), oracle.fptr(rings[j]), D)
         fl = oracle.Filter(); L.zo_filter_init(C.byref(fl))
-        for zf in sh.zf_seq:
+        for _, zf in sh.steps():
             sh.oracle_zero(L, oracle, t, j, zf)
             if filtered:
                 L.zo_filtered_echoes_paint(C.byref(d), C.byref(fl), sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(t0), oracle.fptr(t1), oracle.fptr(t.col(j)), 0.5, 0.2)
@@ -482,14 +561,15 @@ def case_nice(ctx, oracle, sh):
     L = oracle.lib()
     F = sh.F
     m = mod.NiceInstrument(sh.V, sh.gc, ctx); o = sh.out()
-    m.paint(sh.span(), [o], None, True, m.Params(SR, sh.gf, True), zero_first=True)
-    m.paint(sh.span(), [o], None, False, m.Params(SR, sh.gf, False))
+    off_at = 1 if sh.geo.spans is None else 4          # (consecutive spans: the note on through the first four, off from the fifth)
+    for k, zf in sh.steps((True, False)):
+        m.paint(sh.span(), [o], None, k == 0, m.Params(SR, sh.gf, k < off_at), zero_first=zf)
     ref = np.zeros((len(sh.idx), F), np.float32); rs = []
     t0 = np.zeros(F, np.float32); t1 = np.zeros(F, np.float32)
     for j, v in enumerate(sh.idx):
         st = oracle.NiceInstrument(); L.zo_nice_init(C.byref(st), float(sh.color[v]))
-        L.zo_nice_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(t0), oracle.fptr(t1), 1, SR, float(sh.freq[v]), 1)
-        L.zo_nice_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(t0), oracle.fptr(t1), 0, SR, float(sh.freq[v]), 0)
+        for k, _ in sh.steps((True, False)):
+            L.zo_nice_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(t0), oracle.fptr(t1), int(k == 0), SR, float(sh.freq[v]), int(k < off_at))
         rs.append((st.osc.cnt, st.flt.l, st.flt.b, st.env.state, st.env.painter.t, st.env.painter.last_value, st.env.painter.start))
     def states():
         gs = m.state()
@@ -504,6 +584,7 @@ def case_pmosc(ctx, oracle, sh):
     from zang_amd import modules as mod
     L = oracle.lib()
     F = sh.F
+    sh.one_span()
     rel = (0.1 + 0.4 * sh.u2).astype(np.float32)
     m = mod.PMOscInstrument(sh.V, sh.pv(rel), ctx); o = sh.out()
     m.paint(sh.span(), [o], None, True, m.Params(SR, sh.gf, True), zero_first=True)
@@ -530,9 +611,9 @@ def case_noise(ctx, oracle, sh, color, first_zf=True):
     from zang_amd import modules as mod
     L = oracle.lib()
     first = 5000
-    n = sh.e - sh.s                                                                     # (1,024 frames: draws 77, 1001, 1024 + 515)
+    d0, d1, d2 = noise_draws(sh, "noise")                                               # (1,024 frames: draws 77, 1001, 1024 + 515)
     m = mod.Noise(sh.V, ctx, first_seed=first); o = sh.out(fill=0.0)                    # (the first paint may be an ADD)
-    crafted = {int(sh.idx[3]): _crafted_noise_state(77, 1), int(sh.idx[-3]): _crafted_noise_state(n - 23, 2), int(sh.idx[len(sh.idx) // 2]): _crafted_noise_state(n + n // 2 + 3, 3)}
+    crafted = {int(sh.idx[3]): _crafted_noise_state(d0, 1), int(sh.idx[-3]): _crafted_noise_state(d1, 2), int(sh.idx[len(sh.idx) // 2]): _crafted_noise_state(d2, 3)}
     st = m.state()
     for v, r in crafted.items():
         st["r"][v] = r
@@ -540,8 +621,8 @@ def case_noise(ctx, oracle, sh, color, first_zf=True):
     taps[::3] = 0.0
     st["b"][:] = taps
     m.set_state(st)
-    m.paint(sh.span(), [o], [], False, m.Params(color), zero_first=first_zf)
-    m.paint(sh.span(), [o], [], False, m.Params(color))
+    for _, zf in sh.steps((first_zf, False)):
+        m.paint(sh.span(), [o], [], False, m.Params(color), zero_first=zf)
     ref = np.zeros((len(sh.idx), sh.F), np.float32); rs = []
     for j, v in enumerate(sh.idx):
         nz = oracle.Noise(); L.zo_noise_init(C.byref(nz), first + int(v))
@@ -550,7 +631,7 @@ def case_noise(ctx, oracle, sh, color, first_zf=True):
                 nz.r[i] = crafted[int(v)][i]
         for i in range(7):
             nz.b[i] = float(taps[v, i])
-        for _ in range(2):
+        for _ in sh.steps((first_zf, False)):
             L.zo_noise_paint(C.byref(nz), sh.s, sh.e, oracle.fptr(ref[j]), color)
         rs.append(list(nz.r))
     def states():
@@ -563,17 +644,17 @@ def case_noise_filter(ctx, oracle, sh, color):
     from zang_amd import modules as mod
     L = oracle.lib()
     first = 9000
-    n = sh.e - sh.s                                                                     # (1,024 frames: draws 300, 1024 + 9)
+    d0, d1 = noise_draws(sh, "filter")                                                  # (1,024 frames: draws 300, 1024 + 9)
     cutoff = (0.02 + 0.5 * sh.u2).astype(np.float32); res = (0.9 * sh.u3).astype(np.float32)
     m = mod.NoiseFilter(sh.V, ctx, first_seed=first); o = sh.out()
-    crafted = {int(sh.idx[5]): _crafted_noise_state(min(300, n - 21), 4), int(sh.idx[-2]): _crafted_noise_state(n + 9, 5)}
+    crafted = {int(sh.idx[5]): _crafted_noise_state(d0, 4), int(sh.idx[-2]): _crafted_noise_state(d1, 5)}
     st = m.state()
     for v, r in crafted.items():
         st["noise"]["r"][v] = r
     m.set_state(st)
     gcut, gres = sh.pv(cutoff), sh.pv(res)
-    for k in range(2):
-        m.paint(sh.span(), [o], None, False, m.Params(color, mod.Filter.low_pass, gcut, gres), zero_first=(k == 0))
+    for _, zf in sh.steps((True, False)):
+        m.paint(sh.span(), [o], None, False, m.Params(color, mod.Filter.low_pass, gcut, gres), zero_first=zf)
     ref = np.zeros((len(sh.idx), sh.F), np.float32); rs = []
     temp = np.zeros(sh.F, np.float32)
     for j, v in enumerate(sh.idx):
@@ -582,7 +663,7 @@ def case_noise_filter(ctx, oracle, sh, color):
             for i in range(4):
                 nz.r[i] = crafted[int(v)][i]
         fl = oracle.Filter(); L.zo_filter_init(C.byref(fl))
-        for _ in range(2):
+        for _ in sh.steps((True, False)):
             L.zo_zero(sh.s, sh.e, oracle.fptr(temp))
             L.zo_noise_paint(C.byref(nz), sh.s, sh.e, oracle.fptr(temp), color)
             L.zo_filter_paint(C.byref(fl), sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(temp), oracle.FILTER_LOW_PASS, oracle.constant(cutoff[v]), oracle.constant(res[v]))
@@ -597,6 +678,7 @@ def case_noise_filter(ctx, oracle, sh, color):
 def case_curve(ctx, oracle, sh, function):
     from zang_amd import modules as mod
     L = oracle.lib()
+    sh.one_span()
     rng = np.random.default_rng(97)
     ts = np.cumsum(rng.uniform(0.0004, 0.006, 24)).astype(np.float32); ts[0] = 0.0
     vals = rng.uniform(-1, 1, 24).astype(np.float32)
@@ -630,7 +712,7 @@ def case_cycle(ctx, oracle, sh, image):
     ref = t.ref; rt = []
     for j, v in enumerate(sh.idx):
         st = oracle.Cycle(); L.zo_cycle_init(C.byref(st))
-        for zf in sh.zf_seq:
+        for _, zf in sh.steps():
             sh.oracle_zero(L, oracle, t, j, zf)
             L.zo_cycle_paint(C.byref(st), sh.s, sh.e, oracle.fptr(ref[j]), SR, oracle.buffer(t.col(j)) if image else oracle.constant(sh.freq[v]))
         rt.append(st.t)
@@ -640,6 +722,7 @@ def case_cycle(ctx, oracle, sh, image):
 def case_portamento(ctx, oracle, sh):
     from zang_amd import modules as mod, zang
     L = oracle.lib()
+    sh.one_span()
     dur = (0.002 + 0.03 * sh.u2).astype(np.float32)
     goal0 = sh.freq; goal1 = (sh.freq * np.float32(1.5)).astype(np.float32)
     m = mod.Portamento(sh.V, ctx); o = sh.out()
@@ -662,6 +745,7 @@ def case_stateless(ctx, oracle, sh):
     """Gate (bit-exact index arithmetic) and Distortion (both types), frame-chunked kernels without state."""
     from zang_amd import modules as mod
     L = oracle.lib()
+    sh.one_span()
     on = (np.arange(sh.V) % 3 != 1)
     g = mod.Gate(sh.V, ctx); o = sh.out()
     gon = sh.pv(on.astype(np.uint8))
@@ -680,7 +764,7 @@ def case_stateless(ctx, oracle, sh):
         sh.paints(lambda k, zf: d.paint(sh.span(), [t.o], [], False, d.Params(t.src, dtype, ging, goutg, 0.1), zero_first=zf))
         ref = t.ref
         for j, v in enumerate(sh.idx):
-            for zf in sh.zf_seq:
+            for _, zf in sh.steps():
                 sh.oracle_zero(L, oracle, t, j, zf)
                 L.zo_distortion_paint(sh.s, sh.e, oracle.fptr(ref[j]), oracle.fptr(t.col(j)), dtype, float(ing[v]), float(outg[v]), 0.1)
         _check(sh, ctx, f"Distortion type {dtype}", t.o, ref, lambda: [])

@@ -219,3 +219,42 @@ def test_walk_rows_are_the_rows_meant():
     assert {"sine_ranges", "noise_ranges", "decimator_ranges", "script_ranges", "pulse_ctrl_ranges", "nice_pc_max", "nice_pc4_max", "nf_pc_max",
             "nf_ring_max", "filter_pc_max", "filter_pc16_max", "filter_pc_ctl_max", "pink_pipe_max", "echoes_pc_max", "delay_frames_max"} <= set(WALK_ROWS)
     assert not {"script_ranges_maxv", "script_pc_maxv", "filter_tp_max", "nice_wave_max", "basics_rows_min"} & set(WALK_ROWS)
+
+
+class _StepsOnly:
+    """what Shared.steps / pieces and noise_draws need of a Shared, without a device"""
+    zf_seq = (True, False)
+    steps, pieces = pc.Shared.steps, pc.Shared.pieces
+
+    def __init__(self, g):
+        self.geo = g
+        self.s, self.e = g.span
+
+
+def test_crafted_noise_draws_follow_the_span_length():
+    """the positions of the crafted multi-draw samples at every length tests/test_gpu_span_lengths.py paints (noise_draws asserts
+    its own conditions); at 1,024 frames they are the ones the dispatch tests always had"""
+    for L in [0, 1, 2, 3, 4, 5, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 136, 255, 256, 257, 321, 1024, 2047, 2048, 2049, 4103]:
+        sh = _StepsOnly(pc.Geometry("plain", 132, frames=L + 11, span=(5, 5 + L), device="cpu"))
+        a, b, c = pc.noise_draws(sh, "noise")
+        d, e = pc.noise_draws(sh, "filter")
+        assert min(a, b, c, d, e) >= 0
+        if L >= 1:
+            assert a < L and b < L and L <= c < 2 * L and d < L and L <= e < 2 * L, L
+    sh = _StepsOnly(pc.Geometry("plain", 132, frames=1024, device="cpu"))
+    assert pc.noise_draws(sh, "noise") == (77, 1001, 1539) and pc.noise_draws(sh, "filter") == (300, 1033)
+    pieces = [(0, 127), (127, 255), (255, 256), (256, 320), (320, 383), (383, 1200)]
+    sh = _StepsOnly(pc.Geometry("plain", 132, frames=1200, spans=pieces, device="cpu"))
+    a, b, c = pc.noise_draws(sh, "noise")
+    assert a < 127 and 127 + 64 <= b < 255 and 383 + 64 <= c < 1200
+
+
+def test_steps_paint_one_span_twice_or_consecutive_spans_once():
+    sh = _StepsOnly(pc.Geometry("plain", 8, frames=40, span=(3, 30), device="cpu"))
+    assert sh.pieces() == [(3, 30, True), (3, 30, False)] and sh.pieces((False, True, False)) == [(3, 30, False), (3, 30, True), (3, 30, False)]
+    sh = _StepsOnly(pc.Geometry("plain", 8, frames=40, spans=[(2, 9), (9, 10), (10, 33)], device="cpu"))
+    assert sh.geo.span == (2, 33) and (sh.s, sh.e) == (2, 33)
+    assert sh.pieces() == [(2, 9, True), (9, 10, False), (10, 33, False)] and (sh.s, sh.e) == (2, 33)
+    assert sh.pieces((False, False)) == [(2, 9, False), (9, 10, False), (10, 33, False)]
+    with pytest.raises(AssertionError):
+        pc.Geometry("plain", 8, frames=40, spans=[(2, 9), (10, 33)], device="cpu")

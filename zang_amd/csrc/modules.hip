@@ -1631,6 +1631,8 @@ int zh_noise_paint(zh_noise *m, uint32_t start, uint32_t end, const zh_buf *outp
                 if (rc == ZH_OK) {
                     const dim3 grid((m->n + 63) / 64);
                     const long tapsf = zh_form(ZF_PINK_TAPS);             // 0 = the chain of seven stages (k_pink_pipe)
+                    // (`end - start >= 32` below never decides: this branch follows white frame ranges, which zh_noise_range_frames
+                    // gives from 128 frames on -- a shorter pink span is the one loop of k_noise.  tests/test_gpu_span_lengths.py pins it.)
                     const bool taps = tapsf != 0 && end - start >= 32 && outputs[0].stride <= (1u << 24) && m->scratch.stride <= (1u << 24);   // (32-row tiles: 32-bit offsets)
                     if (taps && m->n <= 16384 && tapsf != 16) {   // (ZH_PINK_TAPS=16 forces the 16-frame tiles)
                         if (zf) ZH_LAUNCH((k_pink_taps<true, 32>), grid, dim3(256), 0, st, m->b, m->n, mk_img(outputs[0]), mk_cimg(m->scratch), start, end);
