@@ -1205,6 +1205,80 @@ ZH_API int zh_vibrato_paint_spans(zh_vibrato *m, uint32_t span_start, uint32_t s
                                   const zh_vibrato_params *params, const zh_script_span_param *span_params /*[ZH_VIBRATO_SPAN_FIELDS]*/,
                                   const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :101-110 */
 
+/* ---------------------------------------------------------------- HardSquareInstrument as ONE fused kernel
+ * examples/modules.zig:250-289 (a PulseOsc of color 0.5 times a Gate, the reference's only user of Gate) for n voices, with the
+ * frequency image examples/example_arpeggiator.zig:115 adds beside it (outputs[1], may be a zh_buf whose ptr is NULL: not painted).
+ * Inside a sub-span EVERY frame of outputs[0] gets `+= osc * gate` -- with the gate at 0 and where the PulseOsc paints nothing
+ * (freq < 0 or above sample_rate / 8) too, so -0.0 becomes +0.0 and a non-finite osc shows -- and every frame of outputs[1]
+ * `+= freq`.  PulseOsc's per-paint prologue runs at every sub-span.  note_id_changed reaches no module of this voice.  Semantics of
+ * the span paint: zh_<module>_paint_spans above; ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end) of BOTH outputs,
+ * ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; no host sync: capturable.  ZH_ERR_INVALID: NULL arguments, end < start, an outputs[0]
+ * that is NULL or too small, an outputs[1] that is not NULL and too small, what zh_<module>_paint_spans refuses. */
+typedef struct zh_hard_square zh_hard_square;
+typedef struct zh_hard_square_params {                                                                 /* modules.zig:253-257 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on;          /* broadcast or per-voice device arrays */
+} zh_hard_square_params;
+typedef struct zh_hard_square_state { zh_pulseosc_state osc; } zh_hard_square_state;                   /* :259-260 (the Gate has no state) */
+enum { ZH_HARD_SQUARE_SPAN_FREQ = 0 /* f */, ZH_HARD_SQUARE_SPAN_NOTE_ON /* u */, ZH_HARD_SQUARE_SPAN_FIELDS };
+ZH_API int zh_hard_square_create(zh_ctx *ctx, uint32_t n_voices, zh_hard_square **out);                /* init() modules.zig:262-267 */
+ZH_API int zh_hard_square_destroy(zh_hard_square *m);
+ZH_API int zh_hard_square_get_state(zh_hard_square *m, zh_hard_square_state *host);
+ZH_API int zh_hard_square_set_state(zh_hard_square *m, const zh_hard_square_state *host);
+ZH_API int zh_hard_square_paint(zh_hard_square *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                                const zh_buf *temps /*[2], unused; may be NULL*/, zh_bool note_id_changed,
+                                const zh_hard_square_params *params, uint32_t flags);                  /* modules.zig:269-288, arpeggiator :115 */
+ZH_API int zh_hard_square_paint_spans(zh_hard_square *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                                      const zh_buf *temps, const zh_hard_square_params *params,
+                                      const zh_script_span_param *span_params /*[ZH_HARD_SQUARE_SPAN_FIELDS]*/,
+                                      const zh_script_span_table *table, uint32_t flags);              /* the Trigger loop, arpeggiator :106-116 */
+
+/* ---------------------------------------------------------------- the arpeggiator stage: held keys -> impulses, ON THE DEVICE
+ * Arpeggiator.paint of examples/example_arpeggiator.zig (:49-117) without its instrument, for n players, one lane each: a stage
+ * between a live voice bank and a voice.  INPUT: the sub-span table a live bank of polyphony 1 fills from records
+ * {held_lo, held_hi, on = 1} (MainModule.paint's bare Trigger, :153-156; keyEvent :159-167 pushes the whole held-key mask), as
+ * `in` + held[2] (the `u` arrays of record words 0 and 1), and the key frequencies given at creation (1 to 64 f32, copied to the
+ * device: the caller's a4 * rel_freq).  OUTPUT: the stage's own [span][player] table -- count, start, end, note_id_changed, freq,
+ * note_on -- which any *_paint_spans reads in place through zh_arp_script_table / zh_arp_span_param (field 0 = freq as `f`,
+ * 1 = note_on as `u`).  zh_arp_schedule enqueues ONE kernel: no sync, no copy, capturable.
+ * Per player and per outer sub-span [s, e) that holds a note, in order, exactly Arpeggiator.paint (not at all where the outer
+ * table has no sub-span: state untouched, no rows):
+ *  - note_duration = trunc(0.03f * sample_rate), the product rounded once in f32 (:56); ZH_ERR_INVALID unless 1 <= it < 2^31.
+ *  - while next_frame < out_len (the whole buffer's length, :68): the next held key from last_note + 1, wrapping over n_keys;
+ *    found: a note-on at its frequency, last_note = it; none and last_note set: a note-off at last_note's frequency; none and no
+ *    last_note: nothing.  Every push draws a fresh id; the inner ImpulseQueue accepts 32 a call, last_note and next_id advance
+ *    on a dropped push too.  next_frame += note_duration.
+ *  - next_frame -= out_len once per call (:104): a buffer with k outer sub-spans moves the clock k buffers.
+ *  - the inner Trigger (:106-107) walks [s, e): an impulse at or above e ends the walk (the carried note plays to e, the impulse
+ *    is lost); one below the walk's position is taken at the position (the reference asserts; as zh_trigger_next defines it).
+ *    note_id_changed: trigger.zig:96-99.
+ * The carried note's sample rate is not kept: the voice takes the call's.  OVERFLOW as on a voice bank: a player's list stops at
+ * max_spans, state advances, zh_arp_overflows counts dropped rows.  Capacity: 4 rows at creation, zh_arp_reserve changes it
+ * (invalidates views; ZH_ERR_UNSUPPORTED while a capture records).  zh_arp_reset: init() :38-47 -- all zero, next_id = 1,
+ * last_note = -1.  ZH_ERR_INVALID: NULL arguments, n_keys outside 1..64, max_spans of 0 or above the capacity, a NULL array in
+ * `in` or held, in->max_spans == 0; set_state: a last_note outside -1 .. n_keys - 1. */
+typedef struct zh_arp zh_arp;
+typedef struct zh_arp_state {
+    uint64_t next_frame;                   /* :35 */
+    uint64_t next_id;                      /* the IdGenerator's (:32) */
+    int32_t last_note;                     /* :36; -1 = null */
+    uint32_t has_note;                     /* the inner Trigger's carried note (:34, trigger.zig:41) ... */
+    uint64_t note_id;
+    float freq; uint32_t note_on;          /* ... and its params */
+} zh_arp_state;
+enum { ZH_ARP_SPAN_FREQ = 0 /* f */, ZH_ARP_SPAN_NOTE_ON /* u */, ZH_ARP_SPAN_FIELDS };
+ZH_API int zh_arp_create(zh_ctx *ctx, uint32_t n_players, const float *key_freqs /* host [n_keys] */, uint32_t n_keys, zh_arp **out);
+ZH_API int zh_arp_destroy(zh_arp *arp);
+ZH_API int zh_arp_reset(zh_arp *arp);                                                                  /* init() :38-47 */
+ZH_API int zh_arp_reserve(zh_arp *arp, uint32_t max_rows);
+ZH_API int zh_arp_schedule(zh_arp *arp, float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table *in,
+                           const zh_script_span_param *held /*[2]: held_lo, held_hi*/);                /* :49-107 per outer sub-span */
+ZH_API int zh_arp_script_table(const zh_arp *arp, uint32_t max_spans, zh_script_span_table *out);
+ZH_API int zh_arp_span_param(const zh_arp *arp, uint32_t field /* ZH_ARP_SPAN_* */, zh_script_span_param *out);
+ZH_API int zh_arp_overflows(zh_arp *arp, uint64_t *out);
+ZH_API int zh_arp_get_state(zh_arp *arp, zh_arp_state *host /*[n_players]*/);
+ZH_API int zh_arp_set_state(zh_arp *arp, const zh_arp_state *host);
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

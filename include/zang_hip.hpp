@@ -488,6 +488,68 @@ public:
     }
 };
 
+// HardSquareInstrument of examples/modules.zig (:250-289) for n voices as one fused kernel: a pulse of color 0.5 times a gate, with
+// the frequency image examples/example_arpeggiator.zig:115 adds beside it.  Outputs as Porta's
+class HardSquare {
+    zh_hard_square *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 2;
+    using Params = zh_hard_square_params;
+    using State = zh_hard_square_state;
+    HardSquare(Context &ctx, uint32_t n_voices) { check(zh_hard_square_create(ctx.get(), n_voices, &h_), "zh_hard_square_create"); }
+    ~HardSquare() { if (h_) zh_hard_square_destroy(h_); }
+    HardSquare(const HardSquare &) = delete;
+    HardSquare &operator=(const HardSquare &) = delete;
+    zh_hard_square *get() const { return h_; }
+    void getState(State *host) const { check(zh_hard_square_get_state(h_, host), "zh_hard_square_get_state"); }
+    void setState(const State *host) { check(zh_hard_square_set_state(h_, host), "zh_hard_square_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_hard_square_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_hard_square_paint");
+    }
+    // Arpeggiator.paint's Trigger loop (:106-116) for every voice in one call; span_params = host array [ZH_HARD_SQUARE_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_hard_square_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_hard_square_paint_spans");
+    }
+};
+
+// Arpeggiator.paint of examples/example_arpeggiator.zig (:49-107) without its instrument, for n players on the device: a stage
+// between a live voice bank of polyphony 1 (records {held_lo, held_hi, on = 1}) and a voice's paintSpans
+class Arp {
+    zh_arp *h_ = nullptr;
+
+public:
+    using State = zh_arp_state;
+    Arp(Context &ctx, uint32_t n_players, const float *key_freqs, uint32_t n_keys) {
+        check(zh_arp_create(ctx.get(), n_players, key_freqs, n_keys, &h_), "zh_arp_create");
+    }
+    ~Arp() { if (h_) zh_arp_destroy(h_); }
+    Arp(const Arp &) = delete;
+    Arp &operator=(const Arp &) = delete;
+    zh_arp *get() const { return h_; }
+    void reset() { check(zh_arp_reset(h_), "zh_arp_reset"); }                                     // init() :38-47
+    void reserve(uint32_t max_rows) { check(zh_arp_reserve(h_, max_rows), "zh_arp_reserve"); }
+    // one buffer: `in` and held[2] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param of words 0 and 1)
+    void schedule(float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *held) {
+        check(zh_arp_schedule(h_, sample_rate, out_len, max_spans, &in, held), "zh_arp_schedule");
+    }
+    zh_script_span_table scriptTable(uint32_t max_spans) const {
+        zh_script_span_table t{};
+        check(zh_arp_script_table(h_, max_spans, &t), "zh_arp_script_table");
+        return t;
+    }
+    zh_script_span_param spanParam(uint32_t field) const {
+        zh_script_span_param p{};
+        check(zh_arp_span_param(h_, field, &p), "zh_arp_span_param");
+        return p;
+    }
+    uint64_t overflows() { uint64_t n = 0; check(zh_arp_overflows(h_, &n), "zh_arp_overflows"); return n; }
+    void getState(State *host) const { check(zh_arp_get_state(h_, host), "zh_arp_get_state"); }
+    void setState(const State *host) { check(zh_arp_set_state(h_, host), "zh_arp_set_state"); }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -65,6 +65,9 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 ("zh_laser_paint_spans", "span_params"),
                 ("zh_detuned_paint_spans", "span_params"),
                 ("zh_porta_paint_spans", "span_params"), ("zh_vibrato_paint_spans", "span_params"),
+                ("zh_hard_square_paint_spans", "span_params"),
+                # two entries: held_lo, held_hi; n_keys frequencies
+                ("zh_arp_schedule", "held"), ("zh_arp_create", "key_freqs"),
                 # n effects; the nine nodes of the default effect
                 ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
                 # n samples

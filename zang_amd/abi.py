@@ -320,6 +320,25 @@ class VibratoState(C.Structure):           # zh_vibrato_state: the field order o
 VIBRATO_SPAN_FREQ, VIBRATO_SPAN_NOTE_ON, VIBRATO_SPAN_FIELDS = range(3)
 
 
+class HardSquareParams(C.Structure):       # zh_hard_square_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool)]
+
+
+class HardSquareState(C.Structure):        # zh_hard_square_state: examples/modules.zig:259-260 (the Gate has no state)
+    _fields_ = [("osc", PulseOscState)]
+
+
+HARD_SQUARE_SPAN_FREQ, HARD_SQUARE_SPAN_NOTE_ON, HARD_SQUARE_SPAN_FIELDS = range(3)
+
+
+class ArpState(C.Structure):               # zh_arp_state: examples/example_arpeggiator.zig:31-36 without the instrument
+    _fields_ = [("next_frame", u64), ("next_id", u64), ("last_note", C.c_int32), ("has_note", u32), ("note_id", u64), ("freq", f32),
+                ("note_on", u32)]
+
+
+ARP_SPAN_FREQ, ARP_SPAN_NOTE_ON, ARP_SPAN_FIELDS = range(3)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -658,6 +677,22 @@ SIGNATURES = {
     "zh_vibrato_set_state": (C.c_int, [vp, vp]),
     "zh_vibrato_paint": (C.c_int, _paint(VibratoParams)),
     "zh_vibrato_paint_spans": (C.c_int, _paint_spans(VibratoParams)),
+    "zh_hard_square_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_hard_square_destroy": (C.c_int, [vp]),
+    "zh_hard_square_get_state": (C.c_int, [vp, vp]),
+    "zh_hard_square_set_state": (C.c_int, [vp, vp]),
+    "zh_hard_square_paint": (C.c_int, _paint(HardSquareParams)),
+    "zh_hard_square_paint_spans": (C.c_int, _paint_spans(HardSquareParams)),
+    "zh_arp_create": (C.c_int, [vp, u32, vp, u32, P(vp)]),
+    "zh_arp_destroy": (C.c_int, [vp]),
+    "zh_arp_reset": (C.c_int, [vp]),
+    "zh_arp_reserve": (C.c_int, [vp, u32]),
+    "zh_arp_schedule": (C.c_int, [vp, f32, u32, u32, P(ScriptSpanTable), P(ScriptSpanParam)]),
+    "zh_arp_script_table": (C.c_int, [vp, u32, P(ScriptSpanTable)]),
+    "zh_arp_span_param": (C.c_int, [vp, u32, P(ScriptSpanParam)]),
+    "zh_arp_overflows": (C.c_int, [vp, P(u64)]),
+    "zh_arp_get_state": (C.c_int, [vp, vp]),
+    "zh_arp_set_state": (C.c_int, [vp, vp]),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

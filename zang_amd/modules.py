@@ -972,3 +972,22 @@ class Vibrato(_Lead):
     def _cparams(params):
         p = params.patch or Vibrato.Patch()
         return abi.VibratoParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), abi.VibratoPatch(p.vib_hz, p.depth, p.color))
+
+
+class HardSquare(_Lead):
+    """examples/modules.zig:250-289 HardSquareInstrument: a PulseOsc of color 0.5 times a Gate, as one fused kernel, with the
+    frequency image examples/example_arpeggiator.zig:115 adds beside it (outputs[1]; None or left out: not painted).  Inside a
+    sub-span every frame is added to, with the gate at 0 too.  note_id_changed reaches no module of this voice."""
+    _prefix = "hard_square"
+    _state_ctype = abi.HardSquareState
+    num_temps = 2
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+
+    @staticmethod
+    def _cparams(params):
+        return abi.HardSquareParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on))
