@@ -1279,6 +1279,114 @@ ZH_API int zh_arp_overflows(zh_arp *arp, uint64_t *out);
 ZH_API int zh_arp_get_state(zh_arp *arp, zh_arp_state *host /*[n_players]*/);
 ZH_API int zh_arp_set_state(zh_arp *arp, const zh_arp_state *host);
 
+/* ---------------------------------------------------------------- InnerInstrument of the subsong example as ONE fused kernel
+ * examples/example_subsong.zig:24-68 for n voices: a TriSawOsc of constant frequency (temps[0], zeroed first) times an Envelope
+ * whose three curves are cubed (temps[1], zeroed first), `outputs[0] += temps[0] * temps[1]` (:66).  Inside a sub-span EVERY
+ * frame of outputs[0] gets `+= osc * env` -- where the TriSawOsc paints nothing (freq < 0 or above sample_rate / 8) osc is the
+ * zero of :51, where the Envelope paints nothing (idle; note_on while releasing) env is the zero of :57: -0.0 becomes +0.0 and a
+ * non-finite factor shows.  Both modules' per-paint prologues run at every sub-span; note_id_changed reaches the Envelope.  The
+ * oscillator's f32 phase `t` is state the constant-frequency path never touches.  Semantics of the span paint:
+ * zh_<module>_paint_spans above; ZH_PAINT_ZERO_FIRST is supported, ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; no host sync:
+ * capturable.  ZH_ERR_INVALID: NULL arguments, end < start, an outputs[0] that is NULL or too small, what
+ * zh_<module>_paint_spans refuses. */
+typedef struct zh_saw_env zh_saw_env;
+typedef struct zh_saw_env_patch {          /* the reference's constants; uniform over a call */
+    float color;                           /* 0.0                                    :55 */
+    float attack, decay, release;          /* cubed durations 0.025, 0.1, 0.15       :60-62 */
+    float sustain_volume;                  /* 0.5                                    :63 */
+} zh_saw_env_patch;
+typedef struct zh_saw_env_params {                                                                     /* :27-31 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on;          /* broadcast or per-voice device arrays */
+    zh_saw_env_patch patch;
+} zh_saw_env_params;
+typedef struct zh_saw_env_state { zh_trisawosc_state osc; zh_envelope_state env; } zh_saw_env_state;   /* :33-34 */
+enum { ZH_SAW_ENV_SPAN_FREQ = 0 /* f */, ZH_SAW_ENV_SPAN_NOTE_ON /* u */, ZH_SAW_ENV_SPAN_FIELDS };
+ZH_API int zh_saw_env_patch_default(zh_saw_env_patch *patch);
+ZH_API int zh_saw_env_create(zh_ctx *ctx, uint32_t n_voices, zh_saw_env **out);                        /* init() :36-41 */
+ZH_API int zh_saw_env_destroy(zh_saw_env *m);
+ZH_API int zh_saw_env_get_state(zh_saw_env *m, zh_saw_env_state *host);
+ZH_API int zh_saw_env_set_state(zh_saw_env *m, const zh_saw_env_state *host);
+ZH_API int zh_saw_env_paint(zh_saw_env *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[1]*/,
+                            const zh_buf *temps /*[2], unused; may be NULL*/, zh_bool note_id_changed,
+                            const zh_saw_env_params *params, uint32_t flags);                          /* :43-67 */
+ZH_API int zh_saw_env_paint_spans(zh_saw_env *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[1]*/,
+                                  const zh_buf *temps, const zh_saw_env_params *params,
+                                  const zh_script_span_param *span_params /*[ZH_SAW_ENV_SPAN_FIELDS]*/,
+                                  const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :135-143 */
+
+/* ---------------------------------------------------------------- melody kits: K canned songs resident on the device
+ * A song is what NoteTracker follows (src/zang/notes.zig:130-134, :138-153): events {t seconds, note_id, params {freq, note_on}}
+ * in chronological order.  zh_melody_kit_create copies K of them into one device blob -- melody m is events [offsets[m],
+ * offsets[m + 1]) of `events` -- immutable afterwards; it synchronises and is not capturable; the caller's arrays may be freed on
+ * return.  n_melodies == 0 and empty melodies are legal.  The reference asserts the order (notes.zig:177); here ZH_ERR_INVALID:
+ * NULL arguments (events may be NULL when n_events is 0), a t that is NaN or negative, a t below the one before it in the same
+ * melody, offsets that decrease, an offset above n_events.  Destroy a kit after every stage that plays it. */
+typedef struct zh_melody_kit zh_melody_kit;
+typedef struct zh_melody_event {           /* SongEvent, notes.zig:130-134 */
+    float t;                               /* seconds from the melody's start */
+    uint32_t note_on;
+    uint64_t note_id;
+    float freq; uint32_t reserved;
+} zh_melody_event;
+ZH_API int zh_melody_kit_create(zh_ctx *ctx, const uint32_t *offsets /* host [n_melodies + 1] */, uint32_t n_melodies,
+                                const zh_melody_event *events /* host [n_events] */, uint32_t n_events, zh_melody_kit **out);
+ZH_API int zh_melody_kit_destroy(zh_melody_kit *kit);
+ZH_API int zh_melody_kit_count(const zh_melody_kit *kit, uint32_t *melodies_out, uint32_t *events_out /* may be NULL */);
+
+/* ---------------------------------------------------------------- the subsong stage: notes within notes, ON THE DEVICE
+ * SubtrackPlayer.paint of examples/example_subsong.zig (:122-144) without its instrument, for n players, one lane each: a stage
+ * between a live voice bank and a voice.  INPUT: the sub-span table a live bank of polyphony 1 fills from records
+ * {freq, note_on, melody} (MainModule.paint's Trigger, :176-185; keyEvent :188-201), as `in` + outer[3] (ZH_SUBSONG_IN_*: freq as
+ * `f`, note_on as `u`, melody as `u`), and a melody kit.  OUTPUT: the stage's own [span][player] table -- count, start, end,
+ * note_id_changed, freq, note_on -- which any *_paint_spans reads in place through zh_subsong_script_table /
+ * zh_subsong_span_param (field 0 = freq as `f`, 1 = note_on as `u`).  zh_subsong_schedule enqueues ONE kernel: no sync, no copy,
+ * capturable.  Per player and per outer sub-span [s, e) with (freq_o, on_o, nic_o), in order, exactly SubtrackPlayer.paint:
+ *  - on_o && nic_o (:130-133): next_song_event = 0, t = 0, the inner Trigger forgets its note, and the player's melody is
+ *    latched from this sub-span's `melody` (ignored on every other sub-span); an index at or above K latches
+ *    UINT32_MAX ("no melody"), an empty song.
+ *  - NoteTracker.consume(sample_rate, [s, e)) (notes.zig:162-206) in f32, nothing fused: out_len = e - s (the SUB-SPAN's),
+ *    buf_time = out_len / sample_rate, end_t = t + buf_time; every next event with note_t < end_t becomes an impulse at
+ *    s + min(trunc(((note_t - t) / buf_time) * out_len), out_len - 1), the conversion NaN -> 0 and saturating; t = end_t.  The
+ *    reference's arrays hold 32: a 33rd event of one call advances next_song_event and is dropped.
+ *  - the inner Trigger (:135-136; trigger.zig:80-196) walks [s, e) over those impulses; an impulse below the walk's position (a
+ *    clock that runs backwards: a negative sample rate) is taken at the position (the reference asserts; as zh_trigger_next).
+ *  - one row per inner sub-span: freq = (freq_i * freq_o) / base_freq, two f32 operations in that order (:140), freq_i the
+ *    song's RAW frequency and freq_o THIS outer sub-span's -- the carried note keeps the raw value, so a key change re-scales a
+ *    held melody note; note_on the song's; note_id_changed = (on_o && nic_o) || the inner Trigger's (:137), which compares the
+ *    song's note_id (trigger.zig:96-99): a note-off that shares its note-on's id is not a new note.
+ * Defined where the reference is not.  An outer sub-span with e <= s or e > out_len ends the player's list (out_len is an
+ * argument for this alone).  OVERFLOW as on a voice bank: a player's list stops at max_spans, state advances,
+ * zh_subsong_overflows counts dropped rows.  Capacity: 33 rows at creation (what one outer sub-span can make),
+ * zh_subsong_reserve changes it (invalidates views; ZH_ERR_UNSUPPORTED while a capture records).  A sample_rate that is 0,
+ * negative, NaN or infinite follows the arithmetic above: nothing is refused for the rate.  zh_subsong_reset: init() :104-120 --
+ * all zero, the melody 0 (the reference's one song; UINT32_MAX on an empty kit): an outer note-off with no earlier
+ * note-on runs melody 0 from its start without a reset.  The kit must outlive the stage.  ZH_ERR_INVALID: NULL arguments, a kit of
+ * another context, a base_freq that is NaN, max_spans of 0 or above the capacity, a NULL array in `in` (note_id_changed
+ * included) or outer, in->max_spans == 0; set_state: a melody that is neither below K nor UINT32_MAX. */
+typedef struct zh_subsong zh_subsong;
+typedef struct zh_subsong_state {
+    uint32_t next_song_event;              /* NoteTracker's (notes.zig:140) */
+    float t;                               /* notes.zig:141 */
+    uint32_t melody;                       /* the latched melody, or UINT32_MAX: none */
+    uint32_t has_note;                     /* the inner Trigger's carried note (:102, trigger.zig:41) ... */
+    uint64_t note_id;
+    float freq; uint32_t note_on;          /* ... and its params: the song's raw freq */
+} zh_subsong_state;
+enum { ZH_SUBSONG_IN_FREQ = 0 /* f */, ZH_SUBSONG_IN_NOTE_ON /* u */, ZH_SUBSONG_IN_MELODY /* u */, ZH_SUBSONG_IN_FIELDS };
+enum { ZH_SUBSONG_SPAN_FREQ = 0 /* f */, ZH_SUBSONG_SPAN_NOTE_ON /* u */, ZH_SUBSONG_SPAN_FIELDS };
+ZH_API int zh_subsong_create(zh_ctx *ctx, uint32_t n_players, const zh_melody_kit *kit, float base_freq /* :98 */, zh_subsong **out);
+ZH_API int zh_subsong_destroy(zh_subsong *sub);
+ZH_API int zh_subsong_reset(zh_subsong *sub);                                                          /* init() :104-120 */
+ZH_API int zh_subsong_reserve(zh_subsong *sub, uint32_t max_rows);
+ZH_API int zh_subsong_schedule(zh_subsong *sub, float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table *in,
+                               const zh_script_span_param *outer /*[ZH_SUBSONG_IN_FIELDS]*/);          /* :122-144 per outer sub-span */
+ZH_API int zh_subsong_script_table(const zh_subsong *sub, uint32_t max_spans, zh_script_span_table *out);
+ZH_API int zh_subsong_span_param(const zh_subsong *sub, uint32_t field /* ZH_SUBSONG_SPAN_* */, zh_script_span_param *out);
+ZH_API int zh_subsong_overflows(zh_subsong *sub, uint64_t *out);
+ZH_API int zh_subsong_get_state(zh_subsong *sub, zh_subsong_state *host /*[n_players]*/);
+ZH_API int zh_subsong_set_state(zh_subsong *sub, const zh_subsong_state *host);
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

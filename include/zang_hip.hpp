@@ -550,6 +550,86 @@ public:
     void setState(const State *host) { check(zh_arp_set_state(h_, host), "zh_arp_set_state"); }
 };
 
+// InnerInstrument of examples/example_subsong.zig (:24-68) for n voices as one fused kernel: a sawtooth of constant frequency
+// times an envelope whose curves are cubed; one output
+class SawEnv {
+    zh_saw_env *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 1;
+    static constexpr size_t num_temps = 2;
+    using Params = zh_saw_env_params;
+    using Patch = zh_saw_env_patch;
+    using State = zh_saw_env_state;
+    SawEnv(Context &ctx, uint32_t n_voices) { check(zh_saw_env_create(ctx.get(), n_voices, &h_), "zh_saw_env_create"); }
+    ~SawEnv() { if (h_) zh_saw_env_destroy(h_); }
+    SawEnv(const SawEnv &) = delete;
+    SawEnv &operator=(const SawEnv &) = delete;
+    zh_saw_env *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_saw_env_patch_default(&p), "zh_saw_env_patch_default"); return p; }
+    void getState(State *host) const { check(zh_saw_env_get_state(h_, host), "zh_saw_env_get_state"); }
+    void setState(const State *host) { check(zh_saw_env_set_state(h_, host), "zh_saw_env_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 1> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_saw_env_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_saw_env_paint");
+    }
+    // SubtrackPlayer.paint's Trigger loop (:135-143) for every voice in one call; span_params = host array [ZH_SAW_ENV_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 1> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_saw_env_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_saw_env_paint_spans");
+    }
+};
+
+// K canned songs (src/zang/notes.zig:130-134) on the device: melody m = events [offsets[m], offsets[m + 1]); immutable
+class MelodyKit {
+    zh_melody_kit *h_ = nullptr;
+
+public:
+    using Event = zh_melody_event;
+    MelodyKit(Context &ctx, const uint32_t *offsets, uint32_t n_melodies, const Event *events, uint32_t n_events) {
+        check(zh_melody_kit_create(ctx.get(), offsets, n_melodies, events, n_events, &h_), "zh_melody_kit_create");
+    }
+    ~MelodyKit() { if (h_) zh_melody_kit_destroy(h_); }
+    MelodyKit(const MelodyKit &) = delete;
+    MelodyKit &operator=(const MelodyKit &) = delete;
+    zh_melody_kit *get() const { return h_; }
+    uint32_t count() const { uint32_t k = 0; check(zh_melody_kit_count(h_, &k, nullptr), "zh_melody_kit_count"); return k; }
+};
+
+// SubtrackPlayer.paint of examples/example_subsong.zig (:122-144) without its instrument, for n players on the device: a stage
+// between a live voice bank of polyphony 1 (records {freq, note_on, melody}) and a voice's paintSpans.  The kit outlives the stage
+class Subsong {
+    zh_subsong *h_ = nullptr;
+
+public:
+    using State = zh_subsong_state;
+    Subsong(Context &ctx, uint32_t n_players, const MelodyKit &kit, float base_freq) {
+        check(zh_subsong_create(ctx.get(), n_players, kit.get(), base_freq, &h_), "zh_subsong_create");
+    }
+    ~Subsong() { if (h_) zh_subsong_destroy(h_); }
+    Subsong(const Subsong &) = delete;
+    Subsong &operator=(const Subsong &) = delete;
+    zh_subsong *get() const { return h_; }
+    void reset() { check(zh_subsong_reset(h_), "zh_subsong_reset"); }                             // init() :104-120
+    void reserve(uint32_t max_rows) { check(zh_subsong_reserve(h_, max_rows), "zh_subsong_reserve"); }
+    // one buffer: `in` and outer[ZH_SUBSONG_IN_FIELDS] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param)
+    void schedule(float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *outer) {
+        check(zh_subsong_schedule(h_, sample_rate, out_len, max_spans, &in, outer), "zh_subsong_schedule");
+    }
+    zh_script_span_table scriptTable(uint32_t max_spans) const {
+        zh_script_span_table t{};
+        check(zh_subsong_script_table(h_, max_spans, &t), "zh_subsong_script_table");
+        return t;
+    }
+    zh_script_span_param spanParam(uint32_t field) const {
+        zh_script_span_param p{};
+        check(zh_subsong_span_param(h_, field, &p), "zh_subsong_span_param");
+        return p;
+    }
+    uint64_t overflows() { uint64_t n = 0; check(zh_subsong_overflows(h_, &n), "zh_subsong_overflows"); return n; }
+    void getState(State *host) const { check(zh_subsong_get_state(h_, host), "zh_subsong_get_state"); }
+    void setState(const State *host) { check(zh_subsong_set_state(h_, host), "zh_subsong_set_state"); }
+};
+
 }  // namespace zang
 
 namespace mod {

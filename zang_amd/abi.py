@@ -339,6 +339,35 @@ class ArpState(C.Structure):               # zh_arp_state: examples/example_arpe
 ARP_SPAN_FREQ, ARP_SPAN_NOTE_ON, ARP_SPAN_FIELDS = range(3)
 
 
+class SawEnvPatch(C.Structure):            # zh_saw_env_patch: the constants of examples/example_subsong.zig:55-63
+    _fields_ = [("color", f32), ("attack", f32), ("decay", f32), ("release", f32), ("sustain_volume", f32)]
+
+
+class SawEnvParams(C.Structure):           # zh_saw_env_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool), ("patch", SawEnvPatch)]
+
+
+class SawEnvState(C.Structure):            # zh_saw_env_state: the field order of examples/example_subsong.zig:33-34
+    _fields_ = [("osc", TriSawOscState), ("env", EnvelopeState)]
+
+
+SAW_ENV_SPAN_FREQ, SAW_ENV_SPAN_NOTE_ON, SAW_ENV_SPAN_FIELDS = range(3)
+
+
+class MelodyEvent(C.Structure):            # zh_melody_event: SongEvent, src/zang/notes.zig:130-134
+    _fields_ = [("t", f32), ("note_on", u32), ("note_id", u64), ("freq", f32), ("reserved", u32)]
+
+
+class SubsongState(C.Structure):           # zh_subsong_state: examples/example_subsong.zig:100-102 without the instrument
+    _fields_ = [("next_song_event", u32), ("t", f32), ("melody", u32), ("has_note", u32), ("note_id", u64), ("freq", f32),
+                ("note_on", u32)]
+
+
+SUBSONG_IN_FREQ, SUBSONG_IN_NOTE_ON, SUBSONG_IN_MELODY, SUBSONG_IN_FIELDS = range(4)
+SUBSONG_SPAN_FREQ, SUBSONG_SPAN_NOTE_ON, SUBSONG_SPAN_FIELDS = range(3)
+SUBSONG_NO_MELODY = 0xffffffff
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -693,6 +722,26 @@ SIGNATURES = {
     "zh_arp_overflows": (C.c_int, [vp, P(u64)]),
     "zh_arp_get_state": (C.c_int, [vp, vp]),
     "zh_arp_set_state": (C.c_int, [vp, vp]),
+    "zh_saw_env_patch_default": (C.c_int, [P(SawEnvPatch)]),
+    "zh_saw_env_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_saw_env_destroy": (C.c_int, [vp]),
+    "zh_saw_env_get_state": (C.c_int, [vp, vp]),
+    "zh_saw_env_set_state": (C.c_int, [vp, vp]),
+    "zh_saw_env_paint": (C.c_int, _paint(SawEnvParams)),
+    "zh_saw_env_paint_spans": (C.c_int, _paint_spans(SawEnvParams)),
+    "zh_melody_kit_create": (C.c_int, [vp, vp, u32, vp, u32, P(vp)]),
+    "zh_melody_kit_destroy": (C.c_int, [vp]),
+    "zh_melody_kit_count": (C.c_int, [vp, P(u32), P(u32)]),
+    "zh_subsong_create": (C.c_int, [vp, u32, vp, f32, P(vp)]),
+    "zh_subsong_destroy": (C.c_int, [vp]),
+    "zh_subsong_reset": (C.c_int, [vp]),
+    "zh_subsong_reserve": (C.c_int, [vp, u32]),
+    "zh_subsong_schedule": (C.c_int, [vp, f32, u32, u32, P(ScriptSpanTable), P(ScriptSpanParam)]),
+    "zh_subsong_script_table": (C.c_int, [vp, u32, P(ScriptSpanTable)]),
+    "zh_subsong_span_param": (C.c_int, [vp, u32, P(ScriptSpanParam)]),
+    "zh_subsong_overflows": (C.c_int, [vp, P(u64)]),
+    "zh_subsong_get_state": (C.c_int, [vp, vp]),
+    "zh_subsong_set_state": (C.c_int, [vp, vp]),
     "zh_pow": (C.c_int, [vp, u32, vp, vp, vp]),
     "zh_sin": (C.c_int, [vp, u32, vp, vp]),
     "zh_cos": (C.c_int, [vp, u32, vp, vp]),

@@ -34,15 +34,6 @@ __global__ void __launch_bounds__(kSeqBlock) k_lead_spans(const LeadArgs<typenam
                        [&]() ZH_INLINE_LAMBDA { n.end(); });
     if (live) n.store_state(a.state, a.V, v);
 }
-// every voice has ONE sub-span, the span itself, with its own note_id_changed: a table that holds no arrays
-struct LeadOneSpanP {
-    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
-    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
-    uint32_t K;
-    U32 count, start, end;
-    Nic nic;                                                           // kv = 0 * V + v
-};
-
 // span fields of both voices: ZH_PORTA_SPAN_* == ZH_VIBRATO_SPAN_*
 static_assert((int)ZH_PORTA_SPAN_FREQ == (int)ZH_VIBRATO_SPAN_FREQ && (int)ZH_PORTA_SPAN_NOTE_ON == (int)ZH_VIBRATO_SPAN_NOTE_ON &&
               (int)ZH_PORTA_SPAN_FIELDS == (int)ZH_VIBRATO_SPAN_FIELDS, "the two leads share one Params record");

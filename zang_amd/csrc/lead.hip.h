@@ -180,6 +180,16 @@ struct VibratoLane {
     __device__ __forceinline__ void end() { vib.end(); }                        // SineOsc.zig:40
 };
 
+// every voice has ONE sub-span, the span itself, with its own note_id_changed: a table that holds no arrays (the plain
+// paints of lead.hip and saw_env.hip)
+struct LeadOneSpanP {
+    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
+    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
+    uint32_t K;
+    U32 count, start, end;
+    Nic nic;                                                           // kv = 0 * V + v
+};
+
 // frames [f0, f1) of one voice; `active` = false paints nothing.  outputs[0] goes through frame_loop, input-free.  The second
 // column (O1): a ZERO_FIRST paint stores it frame by frame; an ADD paint hands the image to frame_loop as an INPUT, so that its
 // rows are fetched a chunk ahead like the output's, and stores old + f -- frame_loop reads the rows of chunk k + 1 before chunk k

@@ -991,3 +991,38 @@ class HardSquare(_Lead):
     @staticmethod
     def _cparams(params):
         return abi.HardSquareParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on))
+
+
+class SawEnv(_Lead):
+    """examples/example_subsong.zig:24-68 InnerInstrument: a TriSawOsc of constant frequency times an Envelope whose three curves
+    are cubed, as one fused kernel with one output.  Inside a sub-span every frame is added to, where either module paints
+    nothing too.  note_id_changed reaches the Envelope."""
+    _prefix = "saw_env"
+    _state_ctype = abi.SawEnvState
+    num_outputs = 1
+    num_temps = 2
+
+    @dataclass
+    class Patch:                    # the reference's constants (:55, :60-63)
+        color: float = 0.0
+        attack: float = 0.025       # the three curves are cubed
+        decay: float = 0.1
+        release: float = 0.15
+        sustain_volume: float = 0.5
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        patch: Any = None           # SawEnv.Patch; None = the reference's
+
+    @staticmethod
+    def _outputs(outputs):
+        return (abi.Buf * 1)(as_buf(list(outputs)[0]))
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or SawEnv.Patch()
+        patch = abi.SawEnvPatch(p.color, p.attack, p.decay, p.release, p.sustain_volume)
+        return abi.SawEnvParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), patch)
