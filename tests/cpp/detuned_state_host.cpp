@@ -16,8 +16,8 @@ static zh_detuned_state make(uint32_t v) {
     for (int j = 0; j < 4; j++) s.noise.r[j] = 0x9E3779B97F4A7C15ull * (v + 1) + ((uint64_t)j << 60) + j;
     s.noise_filter.l = 0.5f + (float)v; s.noise_filter.b = -0.0f;
     s.osc.cnt = 0xFFFFFFFFu - v; s.osc.t = 0.25f * (float)v;
-    s.env.state = v % 5; s.env.t = 1.0f / (float)(v + 1); s.env.last_value = ds_float(0x7FC00001u + v); s.env.start = ds_float(0x00000001u + v);
-    s.main_filter.l = -1.5f * (float)v; s.main_filter.b = ds_float(0x80000000u);
+    s.env.state = v % 5; s.env.t = 1.0f / (float)(v + 1); s.env.last_value = zh_bits_f32(0x7FC00001u + v); s.env.start = zh_bits_f32(0x00000001u + v);
+    s.main_filter.l = -1.5f * (float)v; s.main_filter.b = zh_bits_f32(0x80000000u);
     return s;
 }
 

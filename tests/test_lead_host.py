@@ -146,8 +146,9 @@ def test_null_handles_are_refused_and_the_default_patch_is_the_references(x):
 
 
 def test_state_layouts_under_the_sanitizers(tmp_path):
-    """0, 1, 65 and 130 voices of both leads packed into heap blocks of exactly the library's size and read back: every word
-    written once, at [word][voice]; every field of zh_porta_state and zh_vibrato_state back on bits"""
+    """0, 1, 65 and 130 voices of both leads -- and of the four other voices on the same host side: HardSquare, SawEnv, detuned,
+    laser -- packed into heap blocks of exactly the library's size and read back: every word written once, at [word][voice]; every
+    field of the six state structs back on bits"""
     exe = str(tmp_path / "lead_state_host")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            STATE_SRC, "-o", exe])

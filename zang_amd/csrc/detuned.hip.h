@@ -8,15 +8,12 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
-#include "../../include/zang_hip.h"
+#include "span_voice.hip.h"
 
 // ---- the state's layout ------------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of zh_detuned_state; the generator's four u64 as (low, high) pairs.  The taps of
 // zh_noise_state (`b`) are not held: white noise never reads them (Noise.zig:51) and the reference never writes them back (:68).
 enum { DS_RNG = 0, DS_NF_L = 8, DS_NF_B, DS_OSC_CNT, DS_OSC_T, DS_ENV_STATE, DS_ENV_T, DS_ENV_LAST, DS_ENV_START, DS_MF_L, DS_MF_B, kDetunedState };
-
-inline uint32_t ds_bits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
-inline float ds_float(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
 
 // voice v of n: struct -> rows (w = uint32_t[kDetunedState * n]) and back
 inline void ds_pack(const zh_detuned_state &s, uint32_t *w, size_t n, size_t v) {
@@ -24,22 +21,23 @@ inline void ds_pack(const zh_detuned_state &s, uint32_t *w, size_t n, size_t v) 
         w[(size_t)(DS_RNG + 2 * j) * n + v] = (uint32_t)s.noise.r[j];
         w[(size_t)(DS_RNG + 2 * j + 1) * n + v] = (uint32_t)(s.noise.r[j] >> 32);
     }
-    w[(size_t)DS_NF_L * n + v] = ds_bits(s.noise_filter.l); w[(size_t)DS_NF_B * n + v] = ds_bits(s.noise_filter.b);
-    w[(size_t)DS_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)DS_OSC_T * n + v] = ds_bits(s.osc.t);
-    w[(size_t)DS_ENV_STATE * n + v] = s.env.state; w[(size_t)DS_ENV_T * n + v] = ds_bits(s.env.t);
-    w[(size_t)DS_ENV_LAST * n + v] = ds_bits(s.env.last_value); w[(size_t)DS_ENV_START * n + v] = ds_bits(s.env.start);
-    w[(size_t)DS_MF_L * n + v] = ds_bits(s.main_filter.l); w[(size_t)DS_MF_B * n + v] = ds_bits(s.main_filter.b);
+    w[(size_t)DS_NF_L * n + v] = zh_f32_bits(s.noise_filter.l); w[(size_t)DS_NF_B * n + v] = zh_f32_bits(s.noise_filter.b);
+    w[(size_t)DS_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)DS_OSC_T * n + v] = zh_f32_bits(s.osc.t);
+    w[(size_t)DS_ENV_STATE * n + v] = s.env.state; w[(size_t)DS_ENV_T * n + v] = zh_f32_bits(s.env.t);
+    w[(size_t)DS_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)DS_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    w[(size_t)DS_MF_L * n + v] = zh_f32_bits(s.main_filter.l); w[(size_t)DS_MF_B * n + v] = zh_f32_bits(s.main_filter.b);
 }
 inline void ds_unpack(zh_detuned_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));                                          // the taps, `reserved`
     for (int j = 0; j < 4; j++)
         s.noise.r[j] = (uint64_t)w[(size_t)(DS_RNG + 2 * j) * n + v] | ((uint64_t)w[(size_t)(DS_RNG + 2 * j + 1) * n + v] << 32);
-    s.noise_filter.l = ds_float(w[(size_t)DS_NF_L * n + v]); s.noise_filter.b = ds_float(w[(size_t)DS_NF_B * n + v]);
-    s.osc.cnt = w[(size_t)DS_OSC_CNT * n + v]; s.osc.t = ds_float(w[(size_t)DS_OSC_T * n + v]);
-    s.env.state = w[(size_t)DS_ENV_STATE * n + v]; s.env.t = ds_float(w[(size_t)DS_ENV_T * n + v]);
-    s.env.last_value = ds_float(w[(size_t)DS_ENV_LAST * n + v]); s.env.start = ds_float(w[(size_t)DS_ENV_START * n + v]);
-    s.main_filter.l = ds_float(w[(size_t)DS_MF_L * n + v]); s.main_filter.b = ds_float(w[(size_t)DS_MF_B * n + v]);
+    s.noise_filter.l = zh_bits_f32(w[(size_t)DS_NF_L * n + v]); s.noise_filter.b = zh_bits_f32(w[(size_t)DS_NF_B * n + v]);
+    s.osc.cnt = w[(size_t)DS_OSC_CNT * n + v]; s.osc.t = zh_bits_f32(w[(size_t)DS_OSC_T * n + v]);
+    s.env.state = w[(size_t)DS_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)DS_ENV_T * n + v]);
+    s.env.last_value = zh_bits_f32(w[(size_t)DS_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)DS_ENV_START * n + v]);
+    s.main_filter.l = zh_bits_f32(w[(size_t)DS_MF_L * n + v]); s.main_filter.b = zh_bits_f32(w[(size_t)DS_MF_B * n + v]);
 }
+using DetunedLayout = VoiceLayout<zh_detuned_state, kDetunedState, ds_pack, ds_unpack>;
 
 // ---- the lane --------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
@@ -60,9 +58,24 @@ struct DetunedArgs {
     ZkU32P mode;
     const float *sf;                                                  // the span arrays (ZH_DETUNED_SPAN_*), or NULL
     const uint32_t *sn, *sm;
+
+    struct Span { float freq; uint32_t note_on, mode; };              // one sub-span's fields, as the span arrays hold them
+    __device__ __forceinline__ Span defaults(uint32_t v) const { return Span{freq.get(v), note_on.get(v) ? 1u : 0u, mode.get(v)}; }
+    __device__ __forceinline__ Span span(size_t kv, const Span &d) const { return Span{span_f(sf, kv, d.freq), span_u(sn, kv, d.note_on), span_u(sm, kv, d.mode)}; }
 };
 
+// the lane contract of span_voice.hip.h, device and host side
 struct DetunedLane {
+    using Params = zh_detuned_params;
+    using Args = DetunedArgs;
+    using Layout = DetunedLayout;
+    static constexpr int kOutputs = 2;
+    static constexpr int kFields = ZH_DETUNED_SPAN_FIELDS;
+    static constexpr uint8_t kinds[ZH_DETUNED_SPAN_FIELDS] = {SPAN_F, SPAN_U, SPAN_U};
+    static Args args(const zh_voice &m, const Params &p, const zh_script_span_param *sp) {
+        return Args{m.n, m.state, p.sample_rate, p.patch, mk_f32(p.freq), mk_bool(p.note_on), ZkU32P{p.mode.value, p.mode.per_voice},
+                    span_fa(sp, ZH_DETUNED_SPAN_FREQ), span_ua(sp, ZH_DETUNED_SPAN_NOTE_ON), span_ua(sp, ZH_DETUNED_SPAN_MODE)};
+    }
     NoiseLane noise;
     FilterLane nf, mf;
     TriSawOscLane osc;
@@ -83,9 +96,7 @@ struct DetunedLane {
         freq = wide_mul = volume = 0.0f; wide = false;
         nf.begin(ZH_FILTER_LOW_PASS, 0.0f, 0.0f); mf.begin(ZH_FILTER_LOW_PASS, 0.0f, 0.0f);
         osc.begin_ctrl(0.0f, 0.0f);
-        env.sample_rate = 0.0f; env.sustain_volume = 0.0f; env.note_on = false;
-        env.attack = env.decay = env.release = CurveP{ZH_CURVE_CUBED, 0.0f};
-        env.mode = ENV_MODE_NONE; env.cur_tag = ZH_CURVE_CUBED; env.cur_step = env.cur_goal = env.cur_delta = 0.0f; env.m_painted = 0;
+        env.idle(ZH_CURVE_CUBED);
     }
     __device__ __forceinline__ void store_state(uint32_t *st, size_t N, uint32_t v) const {
         uint32_t *s = st + v;
@@ -99,12 +110,12 @@ struct DetunedLane {
         s[(size_t)DS_MF_L * N] = zbits_u(mf.l); s[(size_t)DS_MF_B * N] = zbits_u(mf.b);
     }
     // the prologues of OuterInstrument.paint and Instrument.paint, in the order the stages run
-    __device__ __forceinline__ void begin(const DetunedArgs &a, float freq_, bool note_on, uint32_t mode, bool nic) {
+    __device__ __forceinline__ void begin(const Args &a, const Args::Span &s, bool nic) {
         const zh_detuned_patch &p = a.patch;
         noise.begin();                                                                                  // :140
         nf.begin(ZH_FILTER_LOW_PASS, zcutoff_from_frequency(p.warble_hz, a.sample_rate), 0.0f);         // :142-150
-        wide = (mode & 1u) == 0; wide_mul = p.warble_wide;                                              // :152-154
-        freq = freq_;                                                                                   // :63
+        wide = (s.mode & 1u) == 0; wide_mul = p.warble_wide;                                            // :152-154
+        freq = s.freq;                                                                                  // :63
         osc.begin_ctrl(a.sample_rate, p.color);                                                         // :68-72
         volume = p.volume;                                                                              // :76
         env.sample_rate = a.sample_rate;                                                                // :79-86
@@ -112,7 +123,7 @@ struct DetunedLane {
         env.attack = CurveP{ZH_CURVE_CUBED, p.attack};
         env.decay = CurveP{ZH_CURVE_CUBED, p.decay};
         env.release = CurveP{ZH_CURVE_CUBED, p.release};
-        env.note_on = note_on;
+        env.note_on = s.note_on != 0;
         env.begin(nic);
         mf.begin(ZH_FILTER_LOW_PASS, zcutoff_from_frequency(p.cutoff_hz, a.sample_rate), p.res);        // :90-99
     }
@@ -131,25 +142,4 @@ struct DetunedLane {
     }
     __device__ __forceinline__ void end() { osc.end_ctrl(); }                   // TriSawOsc.zig:155
 };
-
-// frames [f0, f1) of one voice; `active` = false paints nothing.  outputs[0] goes through frame_loop, input-free.  The second
-// column (O1): a ZERO_FIRST paint stores it frame by frame; an ADD paint hands the image to frame_loop as an INPUT, so that its
-// rows are fetched a chunk ahead like the output's, and stores old + f -- frame_loop reads the rows of chunk k + 1 before chunk k
-// is computed and a frame's own row before its body in the tail: a row is never read after it was written.
-template <bool ZF, bool O1>
-__device__ __forceinline__ void detuned_paint_frames(DetunedLane &n, const Img &out, const Img &out1, uint32_t v, uint32_t f0, uint32_t f1, bool active) {
-    constexpr int NIN = (O1 && !ZF) ? 1 : 0;
-    const float *ins[1] = {out1.p};
-    const size_t istr[1] = {out1.stride};
-    const uint32_t voff = v * 4u;
-    frame_loop<8, ZF, NIN>(out.p, v, out.stride, ins, istr, f0, f1, [&](uint32_t i, const float (&x)[1], float &val) ZH_INLINE_LAMBDA {
-        float f = 0.0f;
-        if (active) val = n.frame(f);
-        if constexpr (O1) {
-            if (ZF) zrow_store<1>(zrow_rsrc(out1.p, out1.stride, i), voff, 0, active ? 0.0f + f : 0.0f);
-            else if (active) zrow_store<1>(zrow_rsrc(out1.p, out1.stride, i), voff, 0, x[0] + f);   // :74
-        }
-        return active;
-    });
-}
 #endif   // __HIPCC__

@@ -79,6 +79,15 @@ struct EnvLaneT {
     static __device__ __forceinline__ U u(uint32_t x) { return zsplatu<U>(x); }
     static __device__ __forceinline__ F f(float x) { return zsplat<F>(x); }
 
+    // A voice that paints without a sub-span runs no frame; the per-paint parameters and the running stage, which a paint's
+    // prologue and begin() set, are given their idle values all the same (the voices' load_state; curves of tag `tag`).
+    // patch = false: the sustain volume and the curves are the caller's, set once from a table (fm.hip.h).
+    __device__ __forceinline__ void idle(uint32_t tag, bool patch = true) {
+        sample_rate = 0.0f; if (patch) sustain_volume = f(0.0f); note_on = zmask<M>(false);
+        if (patch) attack = decay = release = CurvePT<W>{tag, f(0.0f)};
+        mode = u(ENV_MODE_NONE); cur_tag = u(tag); cur_step = cur_goal = cur_delta = f(0.0f); m_painted = u(0u);
+    }
+
     // Envelope.zig:33-36 + painter.zig:47-50, for the voices in `c`
     __device__ __forceinline__ void change_state_if(M c, U s) {
         state = zsel(c, s, state);

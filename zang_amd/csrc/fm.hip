@@ -6,6 +6,7 @@
 // tolerant form.
 #include "common.hip.h"
 #include "fm.hip.h"
+#include "span_voice.hip.h"   // zh_f32_bits / zh_bits_f32
 #include <vector>
 #include <string.h>
 
@@ -168,7 +169,7 @@ int zh_fm_get_state(zh_fm *m, zh_fm_state *host) { ZH_GUARD(m ? m->ctx : nullptr
     std::vector<uint32_t> w((size_t)kFmState * n);
     int rc = zh_download(m->ctx, w.data(), m->state, w.size() * 4);
     if (rc) return rc;
-    auto f = [](uint32_t u) { float x; memcpy(&x, &u, 4); return x; };
+    const auto f = zh_bits_f32;
     for (size_t v = 0; v < n; v++)
         for (int op = 0; op < 2; op++) {
             const uint32_t *s = w.data() + (size_t)op * FMS_OP * n + v;
@@ -183,7 +184,7 @@ int zh_fm_set_state(zh_fm *m, const zh_fm_state *host) { ZH_GUARD(m ? m->ctx : n
     if (!m || !host) return ZH_ERR_INVALID;
     const size_t n = m->n;
     std::vector<uint32_t> w((size_t)kFmState * n);
-    auto u = [](float x) { uint32_t b; memcpy(&b, &x, 4); return b; };
+    const auto u = zh_f32_bits;
     for (size_t v = 0; v < n; v++)
         for (int op = 0; op < 2; op++) {
             uint32_t *s = w.data() + (size_t)op * FMS_OP * n + v;

@@ -53,8 +53,7 @@ struct FMOpLane {
         env.release = CurveP{ZH_CURVE_CUBED, c[(size_t)FMC_RELEASE * NI]};
         fb_amount = feedback; waveform = wave;
         step_freq = 0.0f;
-        env.sample_rate = 0.0f; env.note_on = false;
-        env.mode = ENV_MODE_NONE; env.cur_tag = ZH_CURVE_CUBED; env.cur_step = env.cur_goal = env.cur_delta = 0.0f; env.m_painted = 0;
+        env.idle(ZH_CURVE_CUBED, false);
     }
     __device__ __forceinline__ void load_state(const uint32_t *st, uint32_t V, uint32_t v, int op) {
         const uint32_t *s = st + (size_t)op * FMS_OP * V + v;

@@ -1,13 +1,12 @@
 // laser.hip -- the curve-driven sound effect of examples/example_laser.zig (:22-117) as ONE fused kernel per paint:
 //   k_laser<ZF>            LaserPlayer.paint for every voice, one lane per voice (:67-116)
 //   k_laser_spans<ZF, TB>  MainModule's Trigger loop (:149-158) for every voice from a span table, on span_walk's segments
-// and the effect kit (zh_sfx_kit) the voices play from.  Lane object, frame body and the kit's layout: laser.hip.h.  Not built: a
-// wave-per-voice form for a handful of voices, frame ranges, a tolerant form.
-#include "common.hip.h"
-#include "span_walk.hip.h"
+// and the effect kit (zh_sfx_kit) the voices play from.  Lane object, frame body, the state's and the kit's layouts: laser.hip.h;
+// the handle with create / destroy / get_state / set_state: span_voice.hip.h.  The kernels stay the voice's own: the curves'
+// tables live in scratch and a frame's index counts from its sub-span's start.  Not built: a wave-per-voice form for a handful of
+// voices, frame ranges, a tolerant form.
 #include "laser.hip.h"
-#include <vector>
-#include <string.h>
+#include "span_walk.hip.h"
 
 struct zh_sfx_kit {
     zh_ctx *ctx;
@@ -17,11 +16,7 @@ struct zh_sfx_kit {
     std::vector<zh_sfx_effect> effects;  // the entries as zh_sfx_kit_effect hands them out: `nodes` point into the array
 };
 
-struct zh_laser {
-    zh_ctx *ctx;
-    uint32_t n;
-    uint32_t *state;                     // [kLaserState][n]
-};
+struct zh_laser : zh_voice {};
 
 // the values of example_laser.zig:22-38 as {value, t}
 static const zh_curve_node kLaserDefault[9] = {
@@ -43,7 +38,8 @@ __global__ void __launch_bounds__(kSeqBlock) k_laser(const LaserArgs a, const Bo
     n.store_state(a.state, a.V, v);
 }
 
-// TB: SpanWalkP, or the table of one sub-span per voice below.  Idle lanes of the last wave shadow voice 0 read-only and store nothing.
+// TB: SpanWalkP, or OneSpanP (zh_laser_paint under the dispatch row laser_uniform_walk).  Idle lanes of the last wave shadow
+// voice 0 read-only and store nothing.
 template <bool ZF, class TB>
 __global__ void __launch_bounds__(kSeqBlock) k_laser_spans(const LaserArgs a, const TB tb, const Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
@@ -65,15 +61,6 @@ __global__ void __launch_bounds__(kSeqBlock) k_laser_spans(const LaserArgs a, co
                        [&]() ZH_INLINE_LAMBDA { n.end(); });
     if (live) n.store_state(a.state, a.V, v);
 }
-// every voice has ONE sub-span, the span itself, with its own note_id_changed: a table that holds no arrays (zh_laser_paint under
-// the dispatch row laser_uniform_walk)
-struct LaserOneSpanP {
-    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
-    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
-    uint32_t K;
-    U32 count, start, end;
-    Nic nic;                                                           // kv = 0 * V + v
-};
 
 // what both paints check, and the kernel's arguments
 static int laser_args(zh_laser *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_laser_params *p, const zh_script_span_param *sp,
@@ -144,62 +131,11 @@ int zh_sfx_kit_effect(const zh_sfx_kit *kit, uint32_t i, zh_sfx_effect *out) {
     return ZH_OK;
 }
 
-int zh_laser_create(zh_ctx *ctx, uint32_t n, zh_laser **out) { ZH_GUARD(ctx);
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    zh_laser *m = new (std::nothrow) zh_laser();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->state = nullptr;
-    int rc = dev_alloc(&m->state, (size_t)kLaserState * n);
-    if (!rc && n) { hipError_t e = hipMemsetAsync(m->state, 0, (size_t)kLaserState * n * 4, ctx->stream); if (e != hipSuccess) rc = (int)e; }   // init() :57-65
-    if (rc) { (void)hipFree(m->state); delete m; return rc; }
-    *out = m;
-    return ZH_OK;
-}
-
-int zh_laser_destroy(zh_laser *m) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    (void)hipFree(m->state);
-    delete m;
-    return ZH_OK;
-}
-
-int zh_laser_get_state(zh_laser *m, zh_laser_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)kLaserState * n);
-    int rc = zh_download(m->ctx, w.data(), m->state, w.size() * 4);
-    if (rc) return rc;
-    auto f = [](uint32_t u) { float x; memcpy(&x, &u, 4); return x; };
-    auto curve = [&](int at, size_t v) { const uint32_t *s = w.data() + (size_t)at * n + v; return zh_curve_module_state{f(s[0]), s[n], (int32_t)s[2 * n], s[3 * n]}; };
-    for (size_t v = 0; v < n; v++) {
-        host[v].carrier_curve = curve(LS_CARRIER_CURVE, v);
-        host[v].carrier.t = f(w[(size_t)LS_CARRIER_T * n + v]);
-        host[v].modulator_curve = curve(LS_MODULATOR_CURVE, v);
-        host[v].modulator.t = f(w[(size_t)LS_MODULATOR_T * n + v]);
-        host[v].volume_curve = curve(LS_VOLUME_CURVE, v);
-    }
-    return ZH_OK;
-}
-
-int zh_laser_set_state(zh_laser *m, const zh_laser_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)kLaserState * n);
-    auto u = [](float x) { uint32_t b; memcpy(&b, &x, 4); return b; };
-    auto curve = [&](int at, size_t v, const zh_curve_module_state &c) {
-        uint32_t *s = w.data() + (size_t)at * n + v;
-        s[0] = u(c.t); s[n] = c.current_song_note; s[2 * n] = (uint32_t)c.current_song_note_offset; s[3 * n] = c.next_song_note;
-    };
-    for (size_t v = 0; v < n; v++) {
-        curve(LS_CARRIER_CURVE, v, host[v].carrier_curve);
-        w[(size_t)LS_CARRIER_T * n + v] = u(host[v].carrier.t);
-        curve(LS_MODULATOR_CURVE, v, host[v].modulator_curve);
-        w[(size_t)LS_MODULATOR_T * n + v] = u(host[v].modulator.t);
-        curve(LS_VOLUME_CURVE, v, host[v].volume_curve);
-    }
-    return n ? zh_upload(m->ctx, m->state, w.data(), w.size() * 4) : ZH_OK;
-}
+// init() :57-65: every word zero
+int zh_laser_create(zh_ctx *ctx, uint32_t n, zh_laser **out) { ZH_GUARD(ctx); return voice_create(ctx, n, kLaserState, out); }
+int zh_laser_destroy(zh_laser *m) { ZH_GUARD(m ? m->ctx : nullptr); return voice_destroy(m); }
+int zh_laser_get_state(zh_laser *m, zh_laser_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return voice_get_state<LaserLayout>(m, host); }
+int zh_laser_set_state(zh_laser *m, const zh_laser_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return voice_set_state<LaserLayout>(m, host); }
 
 int zh_laser_paint(zh_laser *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps, zh_bool note_id_changed,
                    const zh_laser_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
@@ -214,9 +150,9 @@ int zh_laser_paint(zh_laser *m, uint32_t start, uint32_t end, const zh_buf *outp
     const BoolP nic = mk_bool(note_id_changed);
     const Img out = mk_img(outputs[0]);
     if (zh_form(ZF_LASER_UNIFORM_WALK) > 0) {
-        const LaserOneSpanP tb{1, {1}, {start}, {end}, {nic}};
-        if (zf) ZH_LAUNCH((k_laser_spans<true, LaserOneSpanP>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, tb, out, start, end);
-        else ZH_LAUNCH((k_laser_spans<false, LaserOneSpanP>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, tb, out, start, end);
+        const OneSpanP tb{1, {1}, {start}, {end}, {nic}};
+        if (zf) ZH_LAUNCH((k_laser_spans<true, OneSpanP>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, tb, out, start, end);
+        else ZH_LAUNCH((k_laser_spans<false, OneSpanP>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, tb, out, start, end);
     } else {
         if (zf) ZH_LAUNCH((k_laser<true>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, nic, out, start, end);
         else ZH_LAUNCH((k_laser<false>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, nic, out, start, end);

@@ -1,13 +1,41 @@
 // laser.hip.h -- the sound-effect voice of examples/example_laser.zig (LaserPlayer, :40-117): three Curves (modulator frequency,
 // carrier frequency, volume) drive a phase-modulated pair of SineOscs.  Two parts:
-//   the layout of an effect kit (zh_sfx_kit: K triples of curves, all nodes in one device array beside a descriptor table), as
+//   the state's layout (zh_laser_state <-> [word][voice] rows) and the layout of an effect kit (zh_sfx_kit: K triples of curves, all nodes in one device array beside a descriptor table), as
 //   plain C++ so that a stand-alone harness packs and reads it back under ASan and UBSan (tests/cpp/sfx_kit_host.cpp);
 //   the lane (hipcc only): CurveLane x 3 and SineOscLane x 2 of voices.hip.h, untouched, in the reference's stage order.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
-#include "../../include/zang_hip.h"
+#include "span_voice.hip.h"
+
+// ---- the state's layout ------------------------------------------------------------------------------------------------
+// words per voice, [word][voice], in the order of zh_laser_state (example_laser.zig:51-55); a Curve's four words are
+// t, current_song_note, current_song_note_offset, next_song_note
+enum { LS_CARRIER_CURVE = 0, LS_CARRIER_T = 4, LS_MODULATOR_CURVE = 5, LS_MODULATOR_T = 9, LS_VOLUME_CURVE = 10, kLaserState = 14 };
+
+inline void lz_pack_curve(const zh_curve_module_state &c, uint32_t *s, size_t n) {
+    s[0] = zh_f32_bits(c.t); s[n] = c.current_song_note; s[2 * n] = (uint32_t)c.current_song_note_offset; s[3 * n] = c.next_song_note;
+}
+inline zh_curve_module_state lz_unpack_curve(const uint32_t *s, size_t n) {
+    return zh_curve_module_state{zh_bits_f32(s[0]), s[n], (int32_t)s[2 * n], s[3 * n]};
+}
+// voice v of n: struct -> rows (w = uint32_t[kLaserState * n]) and back
+inline void lz_pack(const zh_laser_state &s, uint32_t *w, size_t n, size_t v) {
+    lz_pack_curve(s.carrier_curve, w + (size_t)LS_CARRIER_CURVE * n + v, n);
+    w[(size_t)LS_CARRIER_T * n + v] = zh_f32_bits(s.carrier.t);
+    lz_pack_curve(s.modulator_curve, w + (size_t)LS_MODULATOR_CURVE * n + v, n);
+    w[(size_t)LS_MODULATOR_T * n + v] = zh_f32_bits(s.modulator.t);
+    lz_pack_curve(s.volume_curve, w + (size_t)LS_VOLUME_CURVE * n + v, n);
+}
+inline void lz_unpack(zh_laser_state &s, const uint32_t *w, size_t n, size_t v) {
+    s.carrier_curve = lz_unpack_curve(w + (size_t)LS_CARRIER_CURVE * n + v, n);
+    s.carrier.t = zh_bits_f32(w[(size_t)LS_CARRIER_T * n + v]);
+    s.modulator_curve = lz_unpack_curve(w + (size_t)LS_MODULATOR_CURVE * n + v, n);
+    s.modulator.t = zh_bits_f32(w[(size_t)LS_MODULATOR_T * n + v]);
+    s.volume_curve = lz_unpack_curve(w + (size_t)LS_VOLUME_CURVE * n + v, n);
+}
+using LaserLayout = VoiceLayout<zh_laser_state, kLaserState, lz_pack, lz_unpack>;
 
 // ---- the kit's layout ------------------------------------------------------------------------------------------------
 // Effect i's curves lie one after the other (modulator, carrier, volume), the effects in the order given.  After the last
@@ -55,10 +83,6 @@ inline void lk_pack(const zh_sfx_effect *effects, uint32_t n, const LkEffectDesc
 #include "seq.hip.h"
 #include "voices.hip.h"
 #include "sample_kit.hip.h"        // ZkU32P
-
-// state words per voice, [word][voice], in the order of zh_laser_state (example_laser.zig:51-55); a Curve's four words are
-// t, current_song_note, current_song_note_offset, next_song_note
-enum { LS_CARRIER_CURVE = 0, LS_CARRIER_T = 4, LS_MODULATOR_CURVE = 5, LS_MODULATOR_T = 9, LS_VOLUME_CURVE = 10, kLaserState = 14 };
 
 struct LaserArgs {
     uint32_t V;

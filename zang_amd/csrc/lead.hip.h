@@ -7,62 +7,50 @@
 //   the state layouts (zh_porta_state, zh_vibrato_state <-> [word][voice] rows) as plain C++, so that a stand-alone harness packs and
 //   reads them back under ASan and UBSan (tests/cpp/lead_state_host.cpp);
 //   the lanes (hipcc only): PortamentoLane, SineOscLane, PulseOscLane (its control-image path) of voices.hip.h and EnvLaneT of
-//   envelope.hip.h, untouched, in the reference's stage order.
+//   envelope.hip.h, untouched, in the reference's stage order; and LeadArgs / LeadVoice, the argument block and the host-side
+//   traits of every voice with this Params record (hard_square.hip.h and saw_env.hip.h too).  The kernel and the host side they
+//   plug into: span_voice.hip.h.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
-#include "../../include/zang_hip.h"
+#include "span_voice.hip.h"
 
 // ---- the states' layouts -----------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of the structs
 enum { PS_PORTA_T = 0, PS_PORTA_LAST, PS_PORTA_START, PS_ENV_STATE, PS_ENV_T, PS_ENV_LAST, PS_ENV_START, PS_OSC_T, PS_PREV_NOTE_ON, kPortaState };
 enum { VS_VIB_T = 0, VS_OSC_CNT, kVibratoState };
 
-inline uint32_t ls_bits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
-inline float ls_float(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
-
 // voice v of n: struct -> rows (w = uint32_t[kPortaState * n]) and back
 inline void ps_pack(const zh_porta_state &s, uint32_t *w, size_t n, size_t v) {
-    w[(size_t)PS_PORTA_T * n + v] = ls_bits(s.porta.t); w[(size_t)PS_PORTA_LAST * n + v] = ls_bits(s.porta.last_value);
-    w[(size_t)PS_PORTA_START * n + v] = ls_bits(s.porta.start);
-    w[(size_t)PS_ENV_STATE * n + v] = s.env.state; w[(size_t)PS_ENV_T * n + v] = ls_bits(s.env.t);
-    w[(size_t)PS_ENV_LAST * n + v] = ls_bits(s.env.last_value); w[(size_t)PS_ENV_START * n + v] = ls_bits(s.env.start);
-    w[(size_t)PS_OSC_T * n + v] = ls_bits(s.osc.t);
+    w[(size_t)PS_PORTA_T * n + v] = zh_f32_bits(s.porta.t); w[(size_t)PS_PORTA_LAST * n + v] = zh_f32_bits(s.porta.last_value);
+    w[(size_t)PS_PORTA_START * n + v] = zh_f32_bits(s.porta.start);
+    w[(size_t)PS_ENV_STATE * n + v] = s.env.state; w[(size_t)PS_ENV_T * n + v] = zh_f32_bits(s.env.t);
+    w[(size_t)PS_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)PS_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    w[(size_t)PS_OSC_T * n + v] = zh_f32_bits(s.osc.t);
     w[(size_t)PS_PREV_NOTE_ON * n + v] = s.prev_note_on;
 }
 inline void ps_unpack(zh_porta_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
-    s.porta.t = ls_float(w[(size_t)PS_PORTA_T * n + v]); s.porta.last_value = ls_float(w[(size_t)PS_PORTA_LAST * n + v]);
-    s.porta.start = ls_float(w[(size_t)PS_PORTA_START * n + v]);
-    s.env.state = w[(size_t)PS_ENV_STATE * n + v]; s.env.t = ls_float(w[(size_t)PS_ENV_T * n + v]);
-    s.env.last_value = ls_float(w[(size_t)PS_ENV_LAST * n + v]); s.env.start = ls_float(w[(size_t)PS_ENV_START * n + v]);
-    s.osc.t = ls_float(w[(size_t)PS_OSC_T * n + v]);
+    s.porta.t = zh_bits_f32(w[(size_t)PS_PORTA_T * n + v]); s.porta.last_value = zh_bits_f32(w[(size_t)PS_PORTA_LAST * n + v]);
+    s.porta.start = zh_bits_f32(w[(size_t)PS_PORTA_START * n + v]);
+    s.env.state = w[(size_t)PS_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)PS_ENV_T * n + v]);
+    s.env.last_value = zh_bits_f32(w[(size_t)PS_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)PS_ENV_START * n + v]);
+    s.osc.t = zh_bits_f32(w[(size_t)PS_OSC_T * n + v]);
     s.prev_note_on = w[(size_t)PS_PREV_NOTE_ON * n + v];
 }
 // ... (w = uint32_t[kVibratoState * n])
 inline void vs_pack(const zh_vibrato_state &s, uint32_t *w, size_t n, size_t v) {
-    w[(size_t)VS_VIB_T * n + v] = ls_bits(s.vib.t);
+    w[(size_t)VS_VIB_T * n + v] = zh_f32_bits(s.vib.t);
     w[(size_t)VS_OSC_CNT * n + v] = s.osc.cnt;
 }
 inline void vs_unpack(zh_vibrato_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
-    s.vib.t = ls_float(w[(size_t)VS_VIB_T * n + v]);
+    s.vib.t = zh_bits_f32(w[(size_t)VS_VIB_T * n + v]);
     s.osc.cnt = w[(size_t)VS_OSC_CNT * n + v];
 }
-// what the generic host side (lead.hip) reads of a voice: its struct, its words, its converters
-struct PortaLayout {
-    using State = zh_porta_state;
-    enum { kWords = kPortaState };
-    static void pack(const State &s, uint32_t *w, size_t n, size_t v) { ps_pack(s, w, n, v); }
-    static void unpack(State &s, const uint32_t *w, size_t n, size_t v) { ps_unpack(s, w, n, v); }
-};
-struct VibratoLayout {
-    using State = zh_vibrato_state;
-    enum { kWords = kVibratoState };
-    static void pack(const State &s, uint32_t *w, size_t n, size_t v) { vs_pack(s, w, n, v); }
-    static void unpack(State &s, const uint32_t *w, size_t n, size_t v) { vs_unpack(s, w, n, v); }
-};
+using PortaLayout = VoiceLayout<zh_porta_state, kPortaState, ps_pack, ps_unpack>;
+using VibratoLayout = VoiceLayout<zh_vibrato_state, kVibratoState, vs_pack, vs_unpack>;
 
 // ---- the lanes -------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
@@ -71,6 +59,11 @@ struct VibratoLayout {
 #include "seq.hip.h"
 #include "envelope.hip.h"
 #include "voices.hip.h"
+
+// the span fields of every voice with this Params record: ZH_PORTA_SPAN_* == ZH_VIBRATO_SPAN_* == ZH_HARD_SQUARE_SPAN_* == ZH_SAW_ENV_SPAN_*
+static_assert((int)ZH_PORTA_SPAN_FREQ == (int)ZH_VIBRATO_SPAN_FREQ && (int)ZH_PORTA_SPAN_NOTE_ON == (int)ZH_VIBRATO_SPAN_NOTE_ON &&
+              (int)ZH_PORTA_SPAN_FIELDS == (int)ZH_VIBRATO_SPAN_FIELDS, "the two leads share one Params record");
+enum { LEAD_SPAN_FREQ = ZH_PORTA_SPAN_FREQ, LEAD_SPAN_NOTE_ON = ZH_PORTA_SPAN_NOTE_ON, LEAD_SPAN_FIELDS = ZH_PORTA_SPAN_FIELDS };
 
 template <class PATCH>
 struct LeadArgs {
@@ -82,13 +75,32 @@ struct LeadArgs {
     BoolP note_on;
     const float *sf;                                                  // the span arrays (ZH_<X>_SPAN_*), or NULL
     const uint32_t *sn;
+
+    struct Span { float freq; uint32_t note_on; };                    // one sub-span's fields, as the span arrays hold them
+    __device__ __forceinline__ Span defaults(uint32_t v) const { return Span{freq.get(v), note_on.get(v) ? 1u : 0u}; }
+    __device__ __forceinline__ Span span(size_t kv, const Span &d) const { return Span{span_f(sf, kv, d.freq), span_u(sn, kv, d.note_on)}; }
 };
 
-// A lead's lane: load_state / store_state, begin(args, freq, note_on, note_id_changed) = the prologue of Instrument.paint,
-// frame(f) -> what is added to outputs[0], f = what is added to outputs[1], end() = its epilogue.  Every `0.0f +` is a zang.zero
-// followed by a module's `+=`: -0.0 becomes +0.0.
-struct PortaLane {
-    using Patch = zh_porta_patch;
+// What span_voice.hip.h's host side reads of a lane with this Params record (sample_rate, freq, note_on; `patch` where the voice has
+// constants): OUTS columns, the two span fields.
+template <class PARAMS, class PATCH, int OUTS>
+struct LeadVoice {
+    using Params = PARAMS;
+    using Patch = PATCH;
+    using Args = LeadArgs<PATCH>;
+    static constexpr int kOutputs = OUTS;
+    static constexpr int kFields = LEAD_SPAN_FIELDS;
+    static constexpr uint8_t kinds[LEAD_SPAN_FIELDS] = {SPAN_F, SPAN_U};
+    static Args args(const zh_voice &m, const PARAMS &p, const PATCH &patch, const zh_script_span_param *sp) {
+        return Args{m.n, m.state, p.sample_rate, patch, mk_f32(p.freq), mk_bool(p.note_on), span_fa(sp, LEAD_SPAN_FREQ), span_ua(sp, LEAD_SPAN_NOTE_ON)};
+    }
+    static Args args(const zh_voice &m, const PARAMS &p, const zh_script_span_param *sp) { return args(m, p, p.patch, sp); }
+};
+
+// A lead's lane (the contract: span_voice.hip.h): begin(args, {freq, note_on}, note_id_changed) = the prologue of
+// Instrument.paint, frame(f) -> what is added to outputs[0], f = what is added to outputs[1], end() = its epilogue.  Every
+// `0.0f +` is a zang.zero followed by a module's `+=`: -0.0 becomes +0.0.
+struct PortaLane : LeadVoice<zh_porta_params, zh_porta_patch, 2> {
     using Layout = PortaLayout;
     PortamentoLane porta;
     EnvLaneCubed env;                                                 // all three curves are cubed (:68-70)
@@ -106,9 +118,7 @@ struct PortaLane {
         cur_note_on = prev_note_on;
         porta.goal = porta.t_step = 0.0f; porta.tag = ZH_CURVE_INSTANTANEOUS; porta.flat = true;
         osc.t_step = osc.inv_sr = 0.0f;
-        env.sample_rate = 0.0f; env.sustain_volume = 0.0f; env.note_on = false;
-        env.attack = env.decay = env.release = CurveP{ZH_CURVE_CUBED, 0.0f};
-        env.mode = ENV_MODE_NONE; env.cur_tag = ZH_CURVE_CUBED; env.cur_step = env.cur_goal = env.cur_delta = 0.0f; env.m_painted = 0;
+        env.idle(ZH_CURVE_CUBED);
     }
     __device__ __forceinline__ void store_state(uint32_t *st, size_t N, uint32_t v) const {
         uint32_t *s = st + v;
@@ -118,8 +128,10 @@ struct PortaLane {
         s[(size_t)PS_OSC_T * N] = zbits_u(osc.t);
         s[(size_t)PS_PREV_NOTE_ON * N] = prev_note_on ? 1u : 0u;
     }
-    __device__ __forceinline__ void begin(const LeadArgs<Patch> &a, float freq, bool note_on, bool nic) {
+    __device__ __forceinline__ void begin(const Args &a, const Args::Span &s, bool nic) {
         const zh_porta_patch &p = a.patch;
+        const float freq = s.freq;
+        const bool note_on = s.note_on != 0;
         porta.begin(a.sample_rate, p.glide_curve, p.glide, freq, note_on, prev_note_on, nic);             // :55-61
         env.sample_rate = a.sample_rate;                                                                  // :65-73
         env.sustain_volume = p.sustain_volume;
@@ -140,8 +152,7 @@ struct PortaLane {
     __device__ __forceinline__ void end() { osc.end(); prev_note_on = cur_note_on; }   // SineOsc.zig:40, then the defer of :51
 };
 
-struct VibratoLane {
-    using Patch = zh_vibrato_patch;
+struct VibratoLane : LeadVoice<zh_vibrato_params, zh_vibrato_patch, 2> {
     using Layout = VibratoLayout;
     SineOscLane vib;
     PulseOscLane osc;
@@ -160,12 +171,12 @@ struct VibratoLane {
         st[(size_t)VS_OSC_CNT * N + v] = osc.cnt;
     }
     // note_id_changed reaches no module of this voice (SineOsc, PulseOsc and Gate ignore it)
-    __device__ __forceinline__ void begin(const LeadArgs<Patch> &a, float freq_, bool note_on, bool) {
+    __device__ __forceinline__ void begin(const Args &a, const Args::Span &s, bool) {
         const zh_vibrato_patch &p = a.patch;
         vib.begin(a.sample_rate, p.vib_hz);                                     // :47-51
-        freq = freq_; depth = p.depth;                                          // :52-55
+        freq = s.freq; depth = p.depth;                                         // :52-55
         osc.begin_ctrl(a.sample_rate, p.color);                                 // :58-62
-        gate = note_on ? 1.0f : 0.0f;                                           // :63-66 (0 + 1.0, or the zeroed temp)
+        gate = s.note_on != 0 ? 1.0f : 0.0f;                                       // :63-66 (0 + 1.0, or the zeroed temp)
     }
     __device__ __forceinline__ float frame(float &f) {
         const float m = 0.0f + vib.template frame<false>(0.0f, 0.0f);           // :46-51
@@ -179,36 +190,4 @@ struct VibratoLane {
     }
     __device__ __forceinline__ void end() { vib.end(); }                        // SineOsc.zig:40
 };
-
-// every voice has ONE sub-span, the span itself, with its own note_id_changed: a table that holds no arrays (the plain
-// paints of lead.hip and saw_env.hip)
-struct LeadOneSpanP {
-    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
-    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
-    uint32_t K;
-    U32 count, start, end;
-    Nic nic;                                                           // kv = 0 * V + v
-};
-
-// frames [f0, f1) of one voice; `active` = false paints nothing.  outputs[0] goes through frame_loop, input-free.  The second
-// column (O1): a ZERO_FIRST paint stores it frame by frame; an ADD paint hands the image to frame_loop as an INPUT, so that its
-// rows are fetched a chunk ahead like the output's, and stores old + f -- frame_loop reads the rows of chunk k + 1 before chunk k
-// is computed and a frame's own row before its body in the tail: a row is never read after it was written.  Inside a sub-span
-// EVERY frame of both columns is added to, a +-0.0 addend included.
-template <bool ZF, bool O1, class L>
-__device__ __forceinline__ void lead_paint_frames(L &n, const Img &out, const Img &out1, uint32_t v, uint32_t f0, uint32_t f1, bool active) {
-    constexpr int NIN = (O1 && !ZF) ? 1 : 0;
-    const float *ins[1] = {out1.p};
-    const size_t istr[1] = {out1.stride};
-    const uint32_t voff = v * 4u;
-    frame_loop<8, ZF, NIN>(out.p, v, out.stride, ins, istr, f0, f1, [&](uint32_t i, const float (&x)[1], float &val) ZH_INLINE_LAMBDA {
-        float f = 0.0f;
-        if (active) val = n.frame(f);
-        if constexpr (O1) {
-            if (ZF) zrow_store<1>(zrow_rsrc(out1.p, out1.stride, i), voff, 0, active ? 0.0f + f : 0.0f);
-            else if (active) zrow_store<1>(zrow_rsrc(out1.p, out1.stride, i), voff, 0, x[0] + f);   // porta :85, vibrato :56
-        }
-        return active;
-    });
-}
 #endif   // __HIPCC__

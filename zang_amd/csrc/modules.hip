@@ -2539,16 +2539,9 @@ struct SamplerKitSpans {
 };
 ZH_MODULE_SPANS_KERNEL(k_sampler_kit_spans)
 // zh_sampler_paint_kit: every voice has ONE sub-span, the span itself, with its own note_id_changed -- the same walk, adapter
-// and frame body over a table that holds no arrays
-struct OneSpanWalkP {
-    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
-    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
-    uint32_t K;
-    U32 count, start, end;
-    Nic nic;                                                           // kv = 0 * V + v
-};
+// and frame body over a table that holds no arrays (span_walk.hip.h OneSpanP)
 template <bool ZF, class A>
-__global__ void __launch_bounds__(kSeqBlock) k_sampler_kit(const typename A::Args a, const OneSpanWalkP tb, const Img out, uint32_t start, uint32_t end) {
+__global__ void __launch_bounds__(kSeqBlock) k_sampler_kit(const typename A::Args a, const OneSpanP tb, const Img out, uint32_t start, uint32_t end) {
     module_spans<ZF, A>(a, tb, out, start, end);
 }
 
@@ -2763,7 +2756,7 @@ int zh_sampler_paint_kit(zh_sampler *m, uint32_t start, uint32_t end, const zh_b
     if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);
-    const OneSpanWalkP tb{1, {1}, {start}, {end}, {mk_bool(note_id_changed)}};
+    const OneSpanP tb{1, {1}, {start}, {end}, {mk_bool(note_id_changed)}};
     const dim3 grid = seq_grid(m->n);
     hipStream_t st = m->ctx->stream;
     if (flags & ZH_PAINT_ZERO_FIRST) ZH_LAUNCH((k_sampler_kit<true, SamplerKitSpans>), grid, dim3(kSeqBlock), 0, st, a, tb, mk_img(outputs[0]), start, end);

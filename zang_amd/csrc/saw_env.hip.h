@@ -1,39 +1,40 @@
 // saw_env.hip.h -- InnerInstrument of examples/example_subsong.zig (:24-68): a TriSawOsc of constant frequency times an Envelope
 // whose three curves are cubed.  Two parts, as lead.hip.h: the state's layout as plain C++ (zh_saw_env_state <-> [word][voice]
 // rows), and the lane (hipcc only): TriSawOscLane of voices.hip.h on its constant-frequency path and EnvLaneCubed of
-// envelope.hip.h, untouched, under lead.hip.h's frame loop over one column.
+// envelope.hip.h, untouched, under span_voice.hip.h's frame loop over one column.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
-#include "../../include/zang_hip.h"
+#include "span_voice.hip.h"
 
 enum { SE_OSC_CNT = 0, SE_OSC_T, SE_ENV_STATE, SE_ENV_T, SE_ENV_LAST, SE_ENV_START, kSawEnvState };   // words per voice, [word][voice]
 
 inline void se_pack(const zh_saw_env_state &s, uint32_t *w, size_t n, size_t v) {
-    auto bits = [](float x) { uint32_t u; memcpy(&u, &x, 4); return u; };
-    w[(size_t)SE_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)SE_OSC_T * n + v] = bits(s.osc.t);
-    w[(size_t)SE_ENV_STATE * n + v] = s.env.state; w[(size_t)SE_ENV_T * n + v] = bits(s.env.t);
-    w[(size_t)SE_ENV_LAST * n + v] = bits(s.env.last_value); w[(size_t)SE_ENV_START * n + v] = bits(s.env.start);
+    w[(size_t)SE_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)SE_OSC_T * n + v] = zh_f32_bits(s.osc.t);
+    w[(size_t)SE_ENV_STATE * n + v] = s.env.state; w[(size_t)SE_ENV_T * n + v] = zh_f32_bits(s.env.t);
+    w[(size_t)SE_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)SE_ENV_START * n + v] = zh_f32_bits(s.env.start);
 }
 inline void se_unpack(zh_saw_env_state &s, const uint32_t *w, size_t n, size_t v) {
-    auto flt = [](uint32_t u) { float x; memcpy(&x, &u, 4); return x; };
     memset(&s, 0, sizeof(s));
-    s.osc.cnt = w[(size_t)SE_OSC_CNT * n + v]; s.osc.t = flt(w[(size_t)SE_OSC_T * n + v]);
-    s.env.state = w[(size_t)SE_ENV_STATE * n + v]; s.env.t = flt(w[(size_t)SE_ENV_T * n + v]);
-    s.env.last_value = flt(w[(size_t)SE_ENV_LAST * n + v]); s.env.start = flt(w[(size_t)SE_ENV_START * n + v]);
+    s.osc.cnt = w[(size_t)SE_OSC_CNT * n + v]; s.osc.t = zh_bits_f32(w[(size_t)SE_OSC_T * n + v]);
+    s.env.state = w[(size_t)SE_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)SE_ENV_T * n + v]);
+    s.env.last_value = zh_bits_f32(w[(size_t)SE_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)SE_ENV_START * n + v]);
 }
+using SawEnvLayout = VoiceLayout<zh_saw_env_state, kSawEnvState, se_pack, se_unpack>;
 
 #if defined(__HIPCC__)
 #include "lead.hip.h"
 
-// The lane contract of lead.hip.h (load_state / store_state, begin, frame, end).  `0.0f +` is the zang.zero of :51 followed by
+// The lane contract of span_voice.hip.h (load_state / store_state, begin, frame, end).  `0.0f +` is the zang.zero of :51 followed by
 // TriSawOsc's `+=`; where the TriSawOsc paints nothing (freq < 0 or above sample_rate / 8, TriSawOsc.zig:84-86) temps[0] stays
 // the zero.  The Envelope adds to a zeroed temps[1] (:57-65) or leaves it (idle, or note_on while releasing: frame_masked's
 // +0.0); zang.multiply (:66) then adds osc * env to EVERY frame of the sub-span.  The constant-frequency TriSawOsc never touches
 // its f32 phase `t` (:37): it is carried through.
-struct SawEnvLane {
-    using Patch = zh_saw_env_patch;
+static_assert((int)ZH_SAW_ENV_SPAN_FREQ == LEAD_SPAN_FREQ && (int)ZH_SAW_ENV_SPAN_NOTE_ON == LEAD_SPAN_NOTE_ON &&
+              (int)ZH_SAW_ENV_SPAN_FIELDS == LEAD_SPAN_FIELDS, "the leads' span fields");
+struct SawEnvLane : LeadVoice<zh_saw_env_params, zh_saw_env_patch, 1> {
+    using Layout = SawEnvLayout;
     TriSawOscLane osc;
     EnvLaneCubed env;
 
@@ -45,9 +46,7 @@ struct SawEnvLane {
         // a paint without a sub-span runs no frame; the fields begin() sets are given values all the same
         osc.sample_rate = 0.0f; osc.saw = true;
         osc.begin_const(1.0f, 0.0f, 0.0f);
-        env.sample_rate = 0.0f; env.sustain_volume = 0.0f; env.note_on = false;
-        env.attack = env.decay = env.release = CurveP{ZH_CURVE_CUBED, 0.0f};
-        env.mode = ENV_MODE_NONE; env.cur_tag = ZH_CURVE_CUBED; env.cur_step = env.cur_goal = env.cur_delta = 0.0f; env.m_painted = 0;
+        env.idle(ZH_CURVE_CUBED);
     }
     __device__ __forceinline__ void store_state(uint32_t *st, size_t N, uint32_t v) const {
         uint32_t *s = st + v;
@@ -55,15 +54,15 @@ struct SawEnvLane {
         s[(size_t)SE_ENV_STATE * N] = env.state; s[(size_t)SE_ENV_T * N] = zbits_u(env.t);
         s[(size_t)SE_ENV_LAST * N] = zbits_u(env.last_value); s[(size_t)SE_ENV_START * N] = zbits_u(env.start);
     }
-    __device__ __forceinline__ void begin(const LeadArgs<Patch> &a, float freq, bool note_on, bool nic) {
+    __device__ __forceinline__ void begin(const Args &a, const Args::Span &s, bool nic) {
         const zh_saw_env_patch &p = a.patch;
-        osc.begin_const(a.sample_rate, freq, p.color);                 // :52-56: the per-paint prologue, at every sub-span
+        osc.begin_const(a.sample_rate, s.freq, p.color);               // :52-56: the per-paint prologue, at every sub-span
         env.sample_rate = a.sample_rate;                               // :58-65
         env.sustain_volume = p.sustain_volume;
         env.attack = CurveP{ZH_CURVE_CUBED, p.attack};
         env.decay = CurveP{ZH_CURVE_CUBED, p.decay};
         env.release = CurveP{ZH_CURVE_CUBED, p.release};
-        env.note_on = note_on;
+        env.note_on = s.note_on != 0;
         env.begin(nic);
     }
     __device__ __forceinline__ float frame(float &f) {

@@ -13,6 +13,15 @@ struct SpanWalkP {
     const uint32_t *count, *start, *end;
     const uint8_t *nic;
 };
+// ... of ONE sub-span per voice, the span itself, with the voice's own note_id_changed: a table that holds no arrays (the plain
+// paints that run a span kernel: zh_sampler_paint_kit, the span voices of span_voice.hip.h, zh_laser_paint)
+struct OneSpanP {
+    struct U32 { uint32_t x; __device__ __forceinline__ uint32_t operator[](size_t) const { return x; } };
+    struct Nic { BoolP b; __device__ __forceinline__ uint8_t operator[](size_t v) const { return b.get((uint32_t)v) ? 1 : 0; } };
+    uint32_t K;
+    U32 count, start, end;
+    Nic nic;                                                           // kv = 0 * V + v
+};
 // ... with the note of each sub-span (zh_span_table): the fused instruments' tables (composite.hip, fm.hip)
 struct NoteSpanTableP {
     uint32_t K;
@@ -136,7 +145,7 @@ __device__ __forceinline__ void span_walk_wave(const TB &tb, uint32_t V, uint32_
 //   inputs(a, in, istr)              the NIN input images
 //   begin(a, kv, nic) / frame(a, x, val) -> painted / end(a)   one paint() call's prologue, frames and epilogue
 // Idle lanes of the last wave shadow voice 0 read-only and store nothing.
-// TB: the table, SpanWalkP or anything that reads like it (modules.hip OneSpanWalkP: one sub-span per voice, no arrays).
+// TB: the table, SpanWalkP or anything that reads like it (OneSpanP: one sub-span per voice, no arrays).
 template <bool ZF, class A, class TB>
 __device__ __forceinline__ void module_spans(const typename A::Args &a, const TB &tb, Img out, uint32_t start, uint32_t end) {
     const uint32_t v0 = blockIdx.x * kSeqBlock + threadIdx.x;
