@@ -1387,6 +1387,88 @@ ZH_API int zh_subsong_overflows(zh_subsong *sub, uint64_t *out);
 ZH_API int zh_subsong_get_state(zh_subsong *sub, zh_subsong_state *host /*[n_players]*/);
 ZH_API int zh_subsong_set_state(zh_subsong *sub, const zh_subsong_state *host);
 
+/* ---------------------------------------------------------------- the merge stage: two span tables into one, ON THE DEVICE
+ * The loop of examples/example_two.zig:93-151 ("an iterator that consumes two source iterators") without its voice, for n
+ * players, one lane each: one voice driven by two impulse streams.  INPUT: two [span][player] tables A and B (e.g. of two live
+ * banks of polyphony 1) with their field arrays, as the source descriptors given at creation name them: n_fields (1..4), the
+ * kind of each ('f' or 'u', as zh_script_span_param), and on_field, the index of the source's note-on field (kind 'u').
+ * OUTPUT: the stage's own table, which any *_paint_spans reads in place through zh_span_merge_script_table /
+ * zh_span_merge_span_param.  Its fields, in order: A's, then B's, each with its declared kind (the words copied as bits), then
+ * n_a + n_b + ZH_SPAN_MERGE_NOTE_ON, + ZH_SPAN_MERGE_NIC_A, + ZH_SPAN_MERGE_NIC_B, all `u`.  zh_span_merge_schedule enqueues ONE
+ * kernel: no sync, no copy, capturable.  The stage keeps no state between buffers (the Triggers live in the banks).
+ * Per player, with span = [0, out_len), cnt_x = min(count_x, in_x->max_spans), ia = ib = 0, pos = 0; while pos < out_len and both
+ * sources have a row left:
+ *    e = min(end_a[ia], end_b[ib]);  e <= pos or e > out_len ends the player's list (defined where the reference is not)
+ *    a row [pos, e) with A's fields of row ia and B's of row ib, nic_a = A's note_id_changed[ia], nic_b = B's [ib],
+ *       note_on = on_a | on_b (:136),  note_id_changed = (nic_a & on_a & !nic_b) | (nic_b & on_b & !nic_a) (:127-129)
+ *    a source whose row ends at e moves to its next row (:139-144; both on a tie);  pos = e
+ * Three consequences of the reference's text, kept: (a) a source's nic STICKS -- it is set on every merged row cut from the same
+ * source row (result0 is the same object until trig0.next runs), only the other source's nic masks it; (b) the sources' `start`
+ * arrays are never read: a source whose first row begins after frame 0 is merged from frame 0 with that row's values; (c)
+ * nothing follows once either source runs out of rows (the break of :150).
+ * OVERFLOW as on a voice bank: a player's list stops at max_spans, zh_span_merge_overflows counts dropped rows.  Capacity: 67
+ * rows at creation (what two 34-row tables can make), zh_span_merge_reserve changes it (invalidates views; ZH_ERR_UNSUPPORTED
+ * while a capture records).  ZH_ERR_INVALID: NULL arguments, a NULL array (start included) or max_spans == 0 in
+ * either table, max_spans of 0 or above the capacity, a field array that lacks the pointer of its kind, n_fields outside 1..4, a
+ * kind that is neither 'f' nor 'u', an on_field that is out of range or not of kind 'u'. */
+typedef struct zh_span_merge zh_span_merge;
+enum { ZH_SPAN_MERGE_MAX_FIELDS = 4 };
+typedef struct zh_span_merge_source {
+    uint32_t n_fields;                     /* 1..ZH_SPAN_MERGE_MAX_FIELDS */
+    uint32_t on_field;                     /* the note-on field: < n_fields, of kind 'u' */
+    uint8_t kinds[4];                      /* 'f' or 'u' per field */
+} zh_span_merge_source;
+/* the stage's own fields, counted from n_fields of A + n_fields of B */
+enum { ZH_SPAN_MERGE_NOTE_ON = 0 /* u */, ZH_SPAN_MERGE_NIC_A /* u */, ZH_SPAN_MERGE_NIC_B /* u */, ZH_SPAN_MERGE_OWN_FIELDS };
+ZH_API int zh_span_merge_create(zh_ctx *ctx, uint32_t n_players, const zh_span_merge_source *a, const zh_span_merge_source *b,
+                                zh_span_merge **out);
+ZH_API int zh_span_merge_destroy(zh_span_merge *m);
+ZH_API int zh_span_merge_reserve(zh_span_merge *m, uint32_t max_rows);
+ZH_API int zh_span_merge_schedule(zh_span_merge *m, uint32_t out_len, uint32_t max_spans,
+                                  const zh_script_span_table *in_a, const zh_script_span_param *fields_a /*[a.n_fields]*/,
+                                  const zh_script_span_table *in_b, const zh_script_span_param *fields_b /*[b.n_fields]*/);   /* :93-151 */
+ZH_API int zh_span_merge_script_table(const zh_span_merge *m, uint32_t max_spans, zh_script_span_table *out);
+ZH_API int zh_span_merge_span_param(const zh_span_merge *m, uint32_t field, zh_script_span_param *out);
+ZH_API int zh_span_merge_overflows(zh_span_merge *m, uint64_t *out);
+
+/* ---------------------------------------------------------------- the two-source TriSaw voice as ONE fused kernel
+ * What one inner span of examples/example_two.zig:109-138 and the multiply of :153 do, for n voices: a TriSawOsc of constant
+ * freq and color with note_id_changed false (temps[0], zeroed first) times an Envelope whose three curves are cubed (temps[1],
+ * zeroed first; it takes the sub-span's note_id_changed), `outputs[0] += temps[0] * temps[1]` on EVERY frame of the sub-span (the
+ * product is rounded, then added; where the TriSawOsc paints nothing -- freq < 0 or above sample_rate / 8 -- or the Envelope
+ * paints nothing, the factor is the zero: -0.0 becomes +0.0 and a non-finite factor shows), and `outputs[1] += freq` (:109, the
+ * oscilloscope sync; outputs[1] may be a zh_buf whose ptr is NULL: not painted).  Both modules' per-paint prologues run at every
+ * sub-span.  ONE DIFFERENCE from the example: it multiplies over the whole buffer (:153), so frames no inner span covers get
+ * `+= 0 * 0` there and a -0.0 already in the output becomes +0.0; the span-paint contract leaves such frames alone.  With
+ * ZH_PAINT_ZERO_FIRST, which the player uses, the two are identical.  Semantics of the span paint: zh_<module>_paint_spans above;
+ * ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end) of BOTH outputs, ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; no host sync:
+ * capturable.  ZH_ERR_INVALID: NULL arguments, end < start, an outputs[0] that is NULL or too small, an outputs[1] that is not
+ * NULL and too small, what zh_<module>_paint_spans refuses. */
+typedef struct zh_dual zh_dual;
+typedef struct zh_dual_patch {             /* the reference's constants; uniform over a call */
+    float attack, decay, release;          /* cubed durations 0.025, 0.1, 1.0        :132-134 */
+    float sustain_volume;                  /* 0.5                                    :135 */
+} zh_dual_patch;
+typedef struct zh_dual_params {
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq, color; zh_bool note_on;   /* broadcast or per-voice device arrays */
+    zh_dual_patch patch;
+} zh_dual_params;
+typedef struct zh_dual_state { zh_trisawosc_state osc; zh_envelope_state env; } zh_dual_state;         /* :36-37 */
+enum { ZH_DUAL_SPAN_FREQ = 0 /* f */, ZH_DUAL_SPAN_COLOR /* f */, ZH_DUAL_SPAN_NOTE_ON /* u */, ZH_DUAL_SPAN_FIELDS };
+ZH_API int zh_dual_patch_default(zh_dual_patch *patch);
+ZH_API int zh_dual_create(zh_ctx *ctx, uint32_t n_voices, zh_dual **out);                              /* init() :52-53 */
+ZH_API int zh_dual_destroy(zh_dual *m);
+ZH_API int zh_dual_get_state(zh_dual *m, zh_dual_state *host);
+ZH_API int zh_dual_set_state(zh_dual *m, const zh_dual_state *host);
+ZH_API int zh_dual_paint(zh_dual *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                         const zh_buf *temps /*[2], unused; may be NULL*/, zh_bool note_id_changed,
+                         const zh_dual_params *params, uint32_t flags);                                /* :109-138, :153 */
+ZH_API int zh_dual_paint_spans(zh_dual *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                               const zh_buf *temps, const zh_dual_params *params,
+                               const zh_script_span_param *span_params /*[ZH_DUAL_SPAN_FIELDS]*/,
+                               const zh_script_span_table *table, uint32_t flags);                     /* the merge loop :101-151 */
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

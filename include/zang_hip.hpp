@@ -630,6 +630,71 @@ public:
     void setState(const State *host) { check(zh_subsong_set_state(h_, host), "zh_subsong_set_state"); }
 };
 
+// The loop of examples/example_two.zig (:93-151) without its voice, for n players on the device: two span tables (two live voice
+// banks of polyphony 1, say) merged into one, which a voice's paintSpans reads in place.  Stateless
+class SpanMerge {
+    zh_span_merge *h_ = nullptr;
+    uint32_t own_ = 0;
+
+public:
+    using Source = zh_span_merge_source;
+    SpanMerge(Context &ctx, uint32_t n_players, const Source &a, const Source &b) : own_(a.n_fields + b.n_fields) {
+        check(zh_span_merge_create(ctx.get(), n_players, &a, &b, &h_), "zh_span_merge_create");
+    }
+    ~SpanMerge() { if (h_) zh_span_merge_destroy(h_); }
+    SpanMerge(const SpanMerge &) = delete;
+    SpanMerge &operator=(const SpanMerge &) = delete;
+    zh_span_merge *get() const { return h_; }
+    void reserve(uint32_t max_rows) { check(zh_span_merge_reserve(h_, max_rows), "zh_span_merge_reserve"); }
+    // one buffer: each source's table and its field arrays [n_fields]
+    void schedule(uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in_a, const zh_script_span_param *fields_a,
+                  const zh_script_span_table &in_b, const zh_script_span_param *fields_b) {
+        check(zh_span_merge_schedule(h_, out_len, max_spans, &in_a, fields_a, &in_b, fields_b), "zh_span_merge_schedule");
+    }
+    zh_script_span_table scriptTable(uint32_t max_spans) const {
+        zh_script_span_table t{};
+        check(zh_span_merge_script_table(h_, max_spans, &t), "zh_span_merge_script_table");
+        return t;
+    }
+    // field: A's, then B's, then ownField(ZH_SPAN_MERGE_NOTE_ON / _NIC_A / _NIC_B)
+    uint32_t ownField(uint32_t which) const { return own_ + which; }
+    zh_script_span_param spanParam(uint32_t field) const {
+        zh_script_span_param p{};
+        check(zh_span_merge_span_param(h_, field, &p), "zh_span_merge_span_param");
+        return p;
+    }
+    uint64_t overflows() { uint64_t n = 0; check(zh_span_merge_overflows(h_, &n), "zh_span_merge_overflows"); return n; }
+};
+
+// What one inner span of examples/example_two.zig (:109-138, :153) does, for n voices as one fused kernel: a TriSawOsc of constant
+// frequency and color times an envelope whose curves are cubed, with the frequency image beside it.  Outputs as Porta's
+class Dual {
+    zh_dual *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 2;
+    using Params = zh_dual_params;
+    using Patch = zh_dual_patch;
+    using State = zh_dual_state;
+    Dual(Context &ctx, uint32_t n_voices) { check(zh_dual_create(ctx.get(), n_voices, &h_), "zh_dual_create"); }
+    ~Dual() { if (h_) zh_dual_destroy(h_); }
+    Dual(const Dual &) = delete;
+    Dual &operator=(const Dual &) = delete;
+    zh_dual *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_dual_patch_default(&p), "zh_dual_patch_default"); return p; }
+    void getState(State *host) const { check(zh_dual_get_state(h_, host), "zh_dual_get_state"); }
+    void setState(const State *host) { check(zh_dual_set_state(h_, host), "zh_dual_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_dual_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_dual_paint");
+    }
+    // the merge loop (:101-151) for every voice in one call; span_params = host array [ZH_DUAL_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_dual_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags), "zh_dual_paint_spans");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

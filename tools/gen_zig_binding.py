@@ -71,6 +71,9 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 ("zh_saw_env_paint_spans", "span_params"),
                 # three entries: freq, note_on, melody; n_melodies + 1 offsets, n_events events
                 ("zh_subsong_schedule", "outer"), ("zh_melody_kit_create", "offsets"), ("zh_melody_kit_create", "events"),
+                # n_fields entries per source
+                ("zh_span_merge_schedule", "fields_a"), ("zh_span_merge_schedule", "fields_b"),
+                ("zh_dual_paint_spans", "span_params"),
                 # n effects; the nine nodes of the default effect
                 ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
                 # n samples

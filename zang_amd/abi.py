@@ -368,6 +368,29 @@ SUBSONG_SPAN_FREQ, SUBSONG_SPAN_NOTE_ON, SUBSONG_SPAN_FIELDS = range(3)
 SUBSONG_NO_MELODY = 0xffffffff
 
 
+class SpanMergeSource(C.Structure):        # zh_span_merge_source: one source of the merge stage (examples/example_two.zig:93-151)
+    _fields_ = [("n_fields", u32), ("on_field", u32), ("kinds", C.c_uint8 * 4)]
+
+
+SPAN_MERGE_MAX_FIELDS = 4
+SPAN_MERGE_NOTE_ON, SPAN_MERGE_NIC_A, SPAN_MERGE_NIC_B, SPAN_MERGE_OWN_FIELDS = range(4)   # counted from A's + B's n_fields
+
+
+class DualPatch(C.Structure):              # zh_dual_patch: the constants of examples/example_two.zig:132-135
+    _fields_ = [("attack", f32), ("decay", f32), ("release", f32), ("sustain_volume", f32)]
+
+
+class DualParams(C.Structure):             # zh_dual_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("color", F32), ("note_on", Bool), ("patch", DualPatch)]
+
+
+class DualState(C.Structure):              # zh_dual_state: the field order of examples/example_two.zig:36-37
+    _fields_ = [("osc", TriSawOscState), ("env", EnvelopeState)]
+
+
+DUAL_SPAN_FREQ, DUAL_SPAN_COLOR, DUAL_SPAN_NOTE_ON, DUAL_SPAN_FIELDS = range(4)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -729,6 +752,20 @@ SIGNATURES = {
     "zh_saw_env_set_state": (C.c_int, [vp, vp]),
     "zh_saw_env_paint": (C.c_int, _paint(SawEnvParams)),
     "zh_saw_env_paint_spans": (C.c_int, _paint_spans(SawEnvParams)),
+    "zh_span_merge_create": (C.c_int, [vp, u32, P(SpanMergeSource), P(SpanMergeSource), P(vp)]),
+    "zh_span_merge_destroy": (C.c_int, [vp]),
+    "zh_span_merge_reserve": (C.c_int, [vp, u32]),
+    "zh_span_merge_schedule": (C.c_int, [vp, u32, u32, P(ScriptSpanTable), P(ScriptSpanParam), P(ScriptSpanTable), P(ScriptSpanParam)]),
+    "zh_span_merge_script_table": (C.c_int, [vp, u32, P(ScriptSpanTable)]),
+    "zh_span_merge_span_param": (C.c_int, [vp, u32, P(ScriptSpanParam)]),
+    "zh_span_merge_overflows": (C.c_int, [vp, P(u64)]),
+    "zh_dual_patch_default": (C.c_int, [P(DualPatch)]),
+    "zh_dual_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_dual_destroy": (C.c_int, [vp]),
+    "zh_dual_get_state": (C.c_int, [vp, vp]),
+    "zh_dual_set_state": (C.c_int, [vp, vp]),
+    "zh_dual_paint": (C.c_int, _paint(DualParams)),
+    "zh_dual_paint_spans": (C.c_int, _paint_spans(DualParams)),
     "zh_melody_kit_create": (C.c_int, [vp, vp, u32, vp, u32, P(vp)]),
     "zh_melody_kit_destroy": (C.c_int, [vp]),
     "zh_melody_kit_count": (C.c_int, [vp, P(u32), P(u32)]),

@@ -1026,3 +1026,36 @@ class SawEnv(_Lead):
         p = params.patch or SawEnv.Patch()
         patch = abi.SawEnvPatch(p.color, p.attack, p.decay, p.release, p.sustain_volume)
         return abi.SawEnvParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), patch)
+
+
+class Dual(_Lead):
+    """examples/example_two.zig:109-138, :153: a TriSawOsc of constant frequency and color times an Envelope whose three curves are
+    cubed, as one fused kernel, with the frequency image of :109 beside it (outputs[1]; None or left out: not painted).  One voice
+    driven by two sources: freq from one, color from the other, note_on and note_id_changed from both (two.SpanMerge).  Inside a
+    sub-span every frame is added to, where either module paints nothing too; frames no sub-span covers are left alone (the
+    example's whole-buffer multiply turns a -0.0 there into +0.0; with zero_first the two are identical)."""
+    _prefix = "dual"
+    _state_ctype = abi.DualState
+    num_temps = 2
+    _span_fields = (("freq", "constant"), ("color", "constant"), ("note_on", "boolean"))
+
+    @dataclass
+    class Patch:                    # the reference's constants (:132-135)
+        attack: float = 0.025       # the three curves are cubed
+        decay: float = 0.1
+        release: float = 1.0
+        sustain_volume: float = 0.5
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        color: Any = 0.5            # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        patch: Any = None           # Dual.Patch; None = the reference's
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or Dual.Patch()
+        patch = abi.DualPatch(p.attack, p.decay, p.release, p.sustain_volume)
+        return abi.DualParams(params.sample_rate, 0, as_f32(params.freq), as_f32(params.color), as_bool(params.note_on), patch)
