@@ -515,37 +515,49 @@ public:
     }
 };
 
-// Arpeggiator.paint of examples/example_arpeggiator.zig (:49-107) without its instrument, for n players on the device: a stage
-// between a live voice bank of polyphony 1 (records {held_lo, held_hi, on = 1}) and a voice's paintSpans
-class Arp {
-    zh_arp *h_ = nullptr;
+// What the stage classes below (Arp, Subsong, SpanMerge) share: the handle and the table side of zh_<stage>_*, by its C functions.
+// `prefix` ("zh_arp") is what an Error names
+template <class H, int (*Destroy)(H *), int (*Reserve)(H *, uint32_t), int (*ScriptTable)(const H *, uint32_t, zh_script_span_table *),
+          int (*SpanParam)(const H *, uint32_t, zh_script_span_param *), int (*Overflows)(H *, uint64_t *)>
+class Stage {
+protected:
+    H *h_ = nullptr;
+    const char *prefix_;
+    explicit Stage(const char *prefix) : prefix_(prefix) {}
+    ~Stage() { if (h_) Destroy(h_); }
+    void checked(int rc, const char *fn) const { if (rc != 0) throw Error(rc, std::string(prefix_) + fn); }
 
 public:
-    using State = zh_arp_state;
-    Arp(Context &ctx, uint32_t n_players, const float *key_freqs, uint32_t n_keys) {
-        check(zh_arp_create(ctx.get(), n_players, key_freqs, n_keys, &h_), "zh_arp_create");
-    }
-    ~Arp() { if (h_) zh_arp_destroy(h_); }
-    Arp(const Arp &) = delete;
-    Arp &operator=(const Arp &) = delete;
-    zh_arp *get() const { return h_; }
-    void reset() { check(zh_arp_reset(h_), "zh_arp_reset"); }                                     // init() :38-47
-    void reserve(uint32_t max_rows) { check(zh_arp_reserve(h_, max_rows), "zh_arp_reserve"); }
-    // one buffer: `in` and held[2] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param of words 0 and 1)
-    void schedule(float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *held) {
-        check(zh_arp_schedule(h_, sample_rate, out_len, max_spans, &in, held), "zh_arp_schedule");
-    }
+    Stage(const Stage &) = delete;
+    Stage &operator=(const Stage &) = delete;
+    H *get() const { return h_; }
+    void reserve(uint32_t max_rows) { checked(Reserve(h_, max_rows), "_reserve"); }               // invalidates views and graphs
     zh_script_span_table scriptTable(uint32_t max_spans) const {
         zh_script_span_table t{};
-        check(zh_arp_script_table(h_, max_spans, &t), "zh_arp_script_table");
+        checked(ScriptTable(h_, max_spans, &t), "_script_table");
         return t;
     }
     zh_script_span_param spanParam(uint32_t field) const {
         zh_script_span_param p{};
-        check(zh_arp_span_param(h_, field, &p), "zh_arp_span_param");
+        checked(SpanParam(h_, field, &p), "_span_param");
         return p;
     }
-    uint64_t overflows() { uint64_t n = 0; check(zh_arp_overflows(h_, &n), "zh_arp_overflows"); return n; }
+    uint64_t overflows() { uint64_t n = 0; checked(Overflows(h_, &n), "_overflows"); return n; }
+};
+
+// Arpeggiator.paint of examples/example_arpeggiator.zig (:49-107) without its instrument, for n players on the device: a stage
+// between a live voice bank of polyphony 1 (records {held_lo, held_hi, on = 1}) and a voice's paintSpans
+class Arp : public Stage<zh_arp, zh_arp_destroy, zh_arp_reserve, zh_arp_script_table, zh_arp_span_param, zh_arp_overflows> {
+public:
+    using State = zh_arp_state;
+    Arp(Context &ctx, uint32_t n_players, const float *key_freqs, uint32_t n_keys) : Stage("zh_arp") {
+        check(zh_arp_create(ctx.get(), n_players, key_freqs, n_keys, &h_), "zh_arp_create");
+    }
+    void reset() { check(zh_arp_reset(h_), "zh_arp_reset"); }                                     // init() :38-47
+    // one buffer: `in` and held[2] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param of words 0 and 1)
+    void schedule(float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *held) {
+        check(zh_arp_schedule(h_, sample_rate, out_len, max_spans, &in, held), "zh_arp_schedule");
+    }
     void getState(State *host) const { check(zh_arp_get_state(h_, host), "zh_arp_get_state"); }
     void setState(const State *host) { check(zh_arp_set_state(h_, host), "zh_arp_set_state"); }
 };
@@ -597,73 +609,39 @@ public:
 
 // SubtrackPlayer.paint of examples/example_subsong.zig (:122-144) without its instrument, for n players on the device: a stage
 // between a live voice bank of polyphony 1 (records {freq, note_on, melody}) and a voice's paintSpans.  The kit outlives the stage
-class Subsong {
-    zh_subsong *h_ = nullptr;
-
+class Subsong : public Stage<zh_subsong, zh_subsong_destroy, zh_subsong_reserve, zh_subsong_script_table, zh_subsong_span_param, zh_subsong_overflows> {
 public:
     using State = zh_subsong_state;
-    Subsong(Context &ctx, uint32_t n_players, const MelodyKit &kit, float base_freq) {
+    Subsong(Context &ctx, uint32_t n_players, const MelodyKit &kit, float base_freq) : Stage("zh_subsong") {
         check(zh_subsong_create(ctx.get(), n_players, kit.get(), base_freq, &h_), "zh_subsong_create");
     }
-    ~Subsong() { if (h_) zh_subsong_destroy(h_); }
-    Subsong(const Subsong &) = delete;
-    Subsong &operator=(const Subsong &) = delete;
-    zh_subsong *get() const { return h_; }
     void reset() { check(zh_subsong_reset(h_), "zh_subsong_reset"); }                             // init() :104-120
-    void reserve(uint32_t max_rows) { check(zh_subsong_reserve(h_, max_rows), "zh_subsong_reserve"); }
     // one buffer: `in` and outer[ZH_SUBSONG_IN_FIELDS] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param)
     void schedule(float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *outer) {
         check(zh_subsong_schedule(h_, sample_rate, out_len, max_spans, &in, outer), "zh_subsong_schedule");
     }
-    zh_script_span_table scriptTable(uint32_t max_spans) const {
-        zh_script_span_table t{};
-        check(zh_subsong_script_table(h_, max_spans, &t), "zh_subsong_script_table");
-        return t;
-    }
-    zh_script_span_param spanParam(uint32_t field) const {
-        zh_script_span_param p{};
-        check(zh_subsong_span_param(h_, field, &p), "zh_subsong_span_param");
-        return p;
-    }
-    uint64_t overflows() { uint64_t n = 0; check(zh_subsong_overflows(h_, &n), "zh_subsong_overflows"); return n; }
     void getState(State *host) const { check(zh_subsong_get_state(h_, host), "zh_subsong_get_state"); }
     void setState(const State *host) { check(zh_subsong_set_state(h_, host), "zh_subsong_set_state"); }
 };
 
 // The loop of examples/example_two.zig (:93-151) without its voice, for n players on the device: two span tables (two live voice
 // banks of polyphony 1, say) merged into one, which a voice's paintSpans reads in place.  Stateless
-class SpanMerge {
-    zh_span_merge *h_ = nullptr;
+class SpanMerge : public Stage<zh_span_merge, zh_span_merge_destroy, zh_span_merge_reserve, zh_span_merge_script_table, zh_span_merge_span_param,
+                               zh_span_merge_overflows> {
     uint32_t own_ = 0;
 
 public:
     using Source = zh_span_merge_source;
-    SpanMerge(Context &ctx, uint32_t n_players, const Source &a, const Source &b) : own_(a.n_fields + b.n_fields) {
+    SpanMerge(Context &ctx, uint32_t n_players, const Source &a, const Source &b) : Stage("zh_span_merge"), own_(a.n_fields + b.n_fields) {
         check(zh_span_merge_create(ctx.get(), n_players, &a, &b, &h_), "zh_span_merge_create");
     }
-    ~SpanMerge() { if (h_) zh_span_merge_destroy(h_); }
-    SpanMerge(const SpanMerge &) = delete;
-    SpanMerge &operator=(const SpanMerge &) = delete;
-    zh_span_merge *get() const { return h_; }
-    void reserve(uint32_t max_rows) { check(zh_span_merge_reserve(h_, max_rows), "zh_span_merge_reserve"); }
     // one buffer: each source's table and its field arrays [n_fields]
     void schedule(uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in_a, const zh_script_span_param *fields_a,
                   const zh_script_span_table &in_b, const zh_script_span_param *fields_b) {
         check(zh_span_merge_schedule(h_, out_len, max_spans, &in_a, fields_a, &in_b, fields_b), "zh_span_merge_schedule");
     }
-    zh_script_span_table scriptTable(uint32_t max_spans) const {
-        zh_script_span_table t{};
-        check(zh_span_merge_script_table(h_, max_spans, &t), "zh_span_merge_script_table");
-        return t;
-    }
-    // field: A's, then B's, then ownField(ZH_SPAN_MERGE_NOTE_ON / _NIC_A / _NIC_B)
+    // spanParam's field: A's, then B's, then ownField(ZH_SPAN_MERGE_NOTE_ON / _NIC_A / _NIC_B)
     uint32_t ownField(uint32_t which) const { return own_ + which; }
-    zh_script_span_param spanParam(uint32_t field) const {
-        zh_script_span_param p{};
-        check(zh_span_merge_span_param(h_, field, &p), "zh_span_merge_span_param");
-        return p;
-    }
-    uint64_t overflows() { uint64_t n = 0; check(zh_span_merge_overflows(h_, &n), "zh_span_merge_overflows"); return n; }
 };
 
 // What one inner span of examples/example_two.zig (:109-138, :153) does, for n voices as one fused kernel: a TriSawOsc of constant

@@ -11,6 +11,7 @@
 #include <inttypes.h>
 #include <vector>
 #include "../../zang_amd/csrc/arp_lane.hip.h"
+#include "../../zang_amd/csrc/span_stage.hip.h"
 
 int main() {
     uint32_t sr_bits, n_keys, out_len, max_spans, n, n_buffers, in_spans;
@@ -25,9 +26,11 @@ int main() {
     for (auto &k : keys) if (scanf("%" SCNu32, &k) != 1) return 2;
     std::vector<uint32_t> state((size_t)kArpState * n);                // [word][player], as arp.hip allocates it
     for (size_t p = 0; p < n; p++) { ArpLane s; arp_init(s); arp_store(s, state.data(), n, p); }
-    const size_t cells = (size_t)max_spans * n;
-    std::vector<uint32_t> count(n), start(cells), end(cells), freq(cells), note_on(cells);
+    const size_t cells = (size_t)max_spans * n;                        // the stage's table at a capacity of max_spans rows
+    std::vector<uint32_t> count(n), start(cells), end(cells), words(2 * cells);
     std::vector<uint8_t> changed(cells);
+    const StageRows table{count.data(), start.data(), end.data(), changed.data(), words.data(), cells};
+    const uint32_t *freq = words.data(), *note_on = words.data() + cells;
     const size_t in_cells = (size_t)in_spans * n;
     for (uint32_t b = 0; b < n_buffers; b++) {
         std::vector<uint32_t> in_count(n), in_start(in_cells), in_end(in_cells), lo(in_cells), hi(in_cells);
@@ -42,15 +45,10 @@ int main() {
         for (size_t p = 0; p < n; p++) {                               // k_arp_schedule's body
             ArpLane s;
             arp_load(s, state.data(), n, p);
-            uint32_t k = 0;
-            arp_buffer(s, keys.data(), n_keys, nd, out_len, in_count[p], in_start.data() + p, in_end.data() + p, lo.data() + p, hi.data() + p, n,
-                       [&](uint32_t s0, uint32_t s1, uint32_t fb, uint32_t on, uint32_t ch) {
-                if (k >= max_spans) { dropped++; return; }
-                const size_t idx = (size_t)k * n + p;
-                start[idx] = s0; end[idx] = s1; freq[idx] = fb; note_on[idx] = on; changed[idx] = (uint8_t)ch;
-                k++;
-            });
-            count[p] = k;
+            StageWriter emit{table, n, p, max_spans, 0, 0};
+            arp_buffer(s, keys.data(), n_keys, nd, out_len, in_count[p], in_start.data() + p, in_end.data() + p, lo.data() + p, hi.data() + p, n, emit);
+            count[p] = emit.k;
+            dropped += emit.dropped;
             arp_store(s, state.data(), n, p);
         }
         printf("B %" PRIu32 " dropped %" PRIu64 "\n", b, dropped);

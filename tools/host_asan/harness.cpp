@@ -2,6 +2,8 @@
 // (tools/host_asan.sh): begin_capture (with and without ZH_CAPTURE_COALESCE), paints of flipper modules (PulseOsc / TriSawOsc in
 // table form, SineOsc as frame ranges), held-back batches (oscillators, stereo mixdowns), the pipelined Noise -> Filter recording,
 // eager paints between replays, end / launch / destroy in every order -- modules before their graphs, the context before its graphs.
+// Before them, once with no player and once with five: a live bank and each span-table stage (arp, subsong, merge) through create,
+// reserve, views, schedule, overflows and destroy (stage_passes).
 // No kernel runs: what is checked is the host bookkeeping (ctx.hip, osc.hip, composite.hip, basics.hip) for memory errors, and at
 // the end that no device allocation, stream or graph is left.
 #include <stdio.h>
@@ -99,9 +101,110 @@ static void paint(Ctx &cx, Mod &m, const Fixed *fx = nullptr) {
     m.painted = rc == ZH_OK;
 }
 
+// The table of one stage, or of a bank, through what they share (csrc/span_stage.hip.h): reserve up, down and to the same
+// capacity, the refusals at the capacity's edges, every view, the overflow count.  Leaves a capacity of `rows`.
+#define MUST(x) do { if (!(x)) { fprintf(stderr, "%s:%d: %s does not hold\n", __FILE__, __LINE__, #x); exit(1); } } while (0)
+template <class H>
+static void table_pass(H *h, int (*reserve)(H *, uint32_t), int (*table)(const H *, uint32_t, zh_script_span_table *),
+                       int (*param)(const H *, uint32_t, zh_script_span_param *), int (*overflows)(H *, uint64_t *), unsigned fields, unsigned rows, unsigned n) {
+    zh_script_span_table t, same;
+    zh_script_span_param p, next;
+    OK(reserve(h, 64)); OK(reserve(h, 2)); OK(reserve(h, rows));
+    OK(table(h, rows, &t));
+    OK(reserve(h, rows));                                             // the same capacity: the views stay
+    OK(table(h, rows, &same));
+    MUST(same.count == t.count && same.start == t.start && same.end == t.end && same.note_id_changed == t.note_id_changed);
+    MUST((t.start != nullptr) == (n != 0));
+    MUST(reserve(h, 0) == ZH_ERR_INVALID && table(h, 0, &same) == ZH_ERR_INVALID && table(h, rows + 1, &same) == ZH_ERR_INVALID);
+    for (unsigned f = 0; f < fields; f++) {
+        OK(param(h, f, &p));
+        MUST(!n || p.f || p.u);
+        if (n && f + 1 < fields) {                                    // one block: fields a plane of capacity x n words apart
+            OK(param(h, f + 1, &next));
+            const uint32_t *a = p.u ? p.u : (const uint32_t *)p.f, *b = next.u ? next.u : (const uint32_t *)next.f;
+            MUST(b - a == (ptrdiff_t)rows * n);
+        }
+    }
+    MUST(param(h, fields, &p) == ZH_ERR_INVALID);
+    uint64_t dropped = 1;
+    OK(overflows(h, &dropped));
+    MUST(dropped == 0);
+}
+// one pass per stage over a live bank of polyphony 1, n players: create, table_pass, schedule, overflows, destroy
+static void stage_passes(unsigned n) {
+    zh_ctx *c;
+    OK(zh_create(&c, 0));
+    const unsigned kRows = 7, kWords = 3;
+    uint64_t dropped = 1;
+    zh_voice_bank *bank;
+    OK(zh_voice_bank_create_live(c, n, 1, kWords * 4, 8, 16, &bank));
+    table_pass(bank, zh_voice_bank_reserve, zh_voice_bank_script_table, zh_voice_bank_span_param, zh_voice_bank_overflows, kWords, kRows, n);
+    zh_span_table st;
+    OK(zh_voice_bank_span_table(bank, kRows, 0, &st));
+    MUST(zh_voice_bank_span_table(bank, kRows + 1, 0, &st) == ZH_ERR_INVALID && zh_voice_bank_span_table(bank, kRows, kWords, &st) == ZH_ERR_INVALID);
+    std::vector<uint32_t> inst, frame, rec;
+    std::vector<uint64_t> ids;
+    for (unsigned i = 0; i < n; i++) { inst.push_back(n - 1 - i); frame.push_back(i); ids.push_back(i + 1); rec.insert(rec.end(), {i, 0u, 1u}); }
+    const zh_bank_impulses batch{n, inst.data(), frame.data(), ids.data(), rec.data()};
+    MUST(zh_voice_bank_schedule_live(bank, 64, kRows + 1, &batch) == ZH_ERR_INVALID);
+    OK(zh_voice_bank_schedule_live(bank, 64, kRows, n ? &batch : nullptr));
+    OK(zh_voice_bank_overflows(bank, &dropped));
+    MUST(dropped == 0);
+    zh_script_span_table in;
+    zh_script_span_param w[kWords], f0 = {}, u1 = {}, u2 = {};
+    OK(zh_voice_bank_script_table(bank, kRows, &in));
+    for (unsigned k = 0; k < kWords; k++) OK(zh_voice_bank_span_param(bank, k, &w[k]));
+    f0.f = w[0].f; u1.u = w[1].u; u2.u = w[2].u;
+    if (!n) { static const uint32_t none = 0; in.count = in.start = in.end = &none; in.note_id_changed = (const uint8_t *)&none; f0.f = (const float *)&none; u1.u = u2.u = &none; }   // no player, no arrays: any address passes the checks
+
+    const float keys[3] = {220.0f, 330.0f, 440.0f};
+    zh_arp *arp;
+    OK(zh_arp_create(c, n, keys, 3, &arp));
+    table_pass(arp, zh_arp_reserve, zh_arp_script_table, zh_arp_span_param, zh_arp_overflows, ZH_ARP_SPAN_FIELDS, kRows, n);
+    const zh_script_span_param held[2] = {u1, u2};
+    MUST(zh_arp_schedule(arp, 48000.0f, 64, kRows + 1, &in, held) == ZH_ERR_INVALID);
+    OK(zh_arp_schedule(arp, 48000.0f, 64, kRows, &in, held));
+    OK(zh_arp_overflows(arp, &dropped));
+    OK(zh_arp_destroy(arp));
+
+    const uint32_t offsets[2] = {0, 2};
+    zh_melody_event ev[2];
+    memset(ev, 0, sizeof ev);
+    ev[0].note_on = 1; ev[0].note_id = 1; ev[0].freq = 440.0f; ev[1].t = 0.5f; ev[1].note_id = 2; ev[1].freq = 440.0f;
+    zh_melody_kit *kit;
+    zh_subsong *sub;
+    OK(zh_melody_kit_create(c, offsets, 1, ev, 2, &kit));
+    OK(zh_subsong_create(c, n, kit, 261.6f, &sub));
+    table_pass(sub, zh_subsong_reserve, zh_subsong_script_table, zh_subsong_span_param, zh_subsong_overflows, ZH_SUBSONG_SPAN_FIELDS, kRows, n);
+    const zh_script_span_param outer[ZH_SUBSONG_IN_FIELDS] = {f0, u1, u2};
+    MUST(zh_subsong_schedule(sub, 48000.0f, 64, kRows + 1, &in, outer) == ZH_ERR_INVALID);
+    OK(zh_subsong_schedule(sub, 48000.0f, 64, kRows, &in, outer));
+    OK(zh_subsong_overflows(sub, &dropped));
+    OK(zh_subsong_destroy(sub));
+    OK(zh_melody_kit_destroy(kit));
+
+    zh_span_merge_source src;
+    memset(&src, 0, sizeof src);
+    src.n_fields = 2; src.on_field = 1; src.kinds[0] = 'f'; src.kinds[1] = 'u';
+    zh_span_merge *merge;
+    OK(zh_span_merge_create(c, n, &src, &src, &merge));
+    table_pass(merge, zh_span_merge_reserve, zh_span_merge_script_table, zh_span_merge_span_param, zh_span_merge_overflows,
+               2 + 2 + ZH_SPAN_MERGE_OWN_FIELDS, kRows, n);
+    const zh_script_span_param fields[2] = {f0, u1};
+    MUST(zh_span_merge_schedule(merge, 64, kRows + 1, &in, fields, &in, fields) == ZH_ERR_INVALID);
+    OK(zh_span_merge_schedule(merge, 64, kRows, &in, fields, &in, fields));
+    OK(zh_span_merge_overflows(merge, &dropped));
+    OK(zh_span_merge_destroy(merge));
+
+    OK(zh_voice_bank_destroy(bank));
+    OK(zh_destroy(c));
+}
+
 int main(int argc, char **argv) {
     const unsigned rounds = argc > 1 ? (unsigned)atoi(argv[1]) : 300, seed = argc > 2 ? (unsigned)atoi(argv[2]) : 1;
     rs ^= (unsigned long long)seed * 0x9e3779b97f4a7c15ull;
+    stage_passes(0);
+    stage_passes(5);
     unsigned long paints = 0, captures = 0, launches = 0, refused = 0, held = 0, held_launches = 0;
     for (unsigned round = 0; round < rounds; round++) {
         Ctx cx; cx.capturing = false; cx.flags = 0;

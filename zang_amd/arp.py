@@ -9,6 +9,7 @@ import numpy as np
 
 from . import abi, modules as mod, zang
 from .bank import LiveVoiceBank
+from .stage import Stage, StageTable
 
 # the outer record: Arpeggiator.Params (:26-29) without the shared sample rate -- note_held as a 64-bit mask in two words, and a
 # byte that is always set for the bank's dispatcher (every push takes slot 0: the bare Trigger of MainModule.paint)
@@ -37,45 +38,19 @@ class ArpKeys:
         return note_id, self.held
 
 
-class ArpTable:
-    """What a span paint takes (zh_script_span_table + zh_script_span_param): a view of the stage's table, no copy."""
-
-    def __init__(self, stage, max_spans):
-        self.stage, self.max_spans, self.n_voices = stage, max_spans, stage.n_players
-        self.tb = abi.ScriptSpanTable()
-        abi.check(stage.lib.zh_arp_script_table(stage.handle, max_spans, C.byref(self.tb)), "zh_arp_script_table")
-        self.arrays = {}
-        for name, field in (("freq", abi.ARP_SPAN_FREQ), ("note_on", abi.ARP_SPAN_NOTE_ON)):
-            sp = abi.ScriptSpanParam()
-            abi.check(stage.lib.zh_arp_span_param(stage.handle, field, C.byref(sp)), "zh_arp_span_param")
-            self.arrays[name] = sp
-
-    def device(self, dev, order):
-        sp = (abi.ScriptSpanParam * abi.SCRIPT_MAX_PARAMS)()
-        for i, name in enumerate(order):
-            if name in self.arrays:
-                sp[i] = self.arrays[name]
-        return self.tb, sp
+ArpTable = StageTable
 
 
-class ArpStage:
+class ArpStage(Stage):
     """zh_arp_*: n players' Arpeggiator.paint without the instrument.  `key_freqs`: 1 to 64 key frequencies (the reference's are
     a4 * key_bindings[i].rel_freq), copied to the device.  schedule() reads the table of a LiveVoiceBank of polyphony 1 whose
     records are HELD_PARAMS and fills the stage's own table (script_table())."""
+    PREFIX = "zh_arp"
+    FIELDS = (("freq", abi.ARP_SPAN_FREQ), ("note_on", abi.ARP_SPAN_NOTE_ON))
 
     def __init__(self, ctx, n_players, key_freqs, rows=None):
-        self.ctx, self.lib, self.n_players = ctx, ctx.lib, int(n_players)
         self.key_freqs = np.ascontiguousarray(np.asarray(key_freqs, np.float32).reshape(-1))
-        self.handle = C.c_void_p()
-        abi.check(self.lib.zh_arp_create(ctx.handle, self.n_players, self.key_freqs.ctypes.data, len(self.key_freqs), C.byref(self.handle)),
-                  "zh_arp_create")
-        ctx._children.add(self)
-        if rows is not None:
-            self.reserve(rows)
-
-    def reserve(self, rows):
-        """table capacity in rows; invalidates views and graphs made before it"""
-        abi.check(self.lib.zh_arp_reserve(self.handle, rows), "zh_arp_reserve")
+        self._create(ctx, n_players, rows, self.key_freqs.ctypes.data, len(self.key_freqs))
 
     def reset(self):
         abi.check(self.lib.zh_arp_reset(self.handle), "zh_arp_reset")
@@ -88,15 +63,6 @@ class ArpStage:
     def schedule(self, sample_rate, out_len, max_spans, outer):
         """one buffer: enqueued, no sync"""
         abi.check(self._schedule(sample_rate, out_len, max_spans, outer), "zh_arp_schedule")
-
-    def script_table(self, max_spans):
-        return ArpTable(self, max_spans)
-
-    def overflows(self):
-        """rows dropped so far because a player's list was full (synchronises)"""
-        n = C.c_uint64()
-        abi.check(self.lib.zh_arp_overflows(self.handle, C.byref(n)), "zh_arp_overflows")
-        return n.value
 
     def state(self):
         st = np.zeros(max(self.n_players, 1), np.dtype(abi.ArpState))
@@ -111,28 +77,7 @@ class ArpStage:
     def download(self, max_spans):
         """the stage's table as host arrays (synchronises; for tests and debugging): count [N], start / end / note_on [K][N]
         uint32, freq [K][N] float32, nic [K][N] uint8.  Rows at or above a player's count hold whatever was there."""
-        N, K = self.n_players, max_spans
-        t = self.script_table(K)
-
-        def down(ptr, shape, dtype):
-            a = np.zeros(shape, dtype)
-            if a.size:
-                abi.check(self.lib.zh_download(self.ctx.handle, a.ctypes.data, ptr, a.nbytes), "zh_download")
-            return a
-        return {"count": down(t.tb.count, (N,), np.uint32), "start": down(t.tb.start, (K, N), np.uint32), "end": down(t.tb.end, (K, N), np.uint32),
-                "nic": down(t.tb.note_id_changed, (K, N), np.uint8), "freq": down(t.arrays["freq"].f, (K, N), np.float32),
-                "note_on": down(t.arrays["note_on"].u, (K, N), np.uint32)}
-
-    def close(self):
-        if self.handle:
-            self.lib.zh_arp_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:       # noqa: BLE001
-            pass
+        return super().download(max_spans, {"freq": np.float32})
 
 
 def held_table(bank, max_spans):

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
+from .stage import SpanTableView
 
 
 class BankSpanTable:
@@ -17,7 +18,7 @@ class BankSpanTable:
         abi.check(bank.lib.zh_voice_bank_span_table(bank.handle, max_spans, freq_word, C.byref(self.c)), "zh_voice_bank_span_table")
 
 
-class BankScriptTable:
+class BankScriptTable(SpanTableView):
     """What ScriptModule.paint_spans and the builtin modules' paint_spans take (zh_script_span_table + zh_script_span_param): a
     view of the bank's tables.  `fields`: {param name: (record word, "f" or "u")} -- "u" for a boolean (its byte first in an
     otherwise zero word) or an enum's index; `constants`: {param name: value} shared by every sub-span."""
@@ -33,13 +34,6 @@ class BankScriptTable:
             sp = abi.ScriptSpanParam()
             abi.check(bank.lib.zh_voice_bank_span_param(bank.handle, word, C.byref(sp)), "zh_voice_bank_span_param")
             self.arrays[name] = abi.ScriptSpanParam(sp.f if view == "f" else None, sp.u if view == "u" else None)
-
-    def device(self, dev, order):
-        sp = (abi.ScriptSpanParam * abi.SCRIPT_MAX_PARAMS)()
-        for i, name in enumerate(order):
-            if name in self.arrays:
-                sp[i] = self.arrays[name]
-        return self.tb, sp
 
 
 class VoiceBank:

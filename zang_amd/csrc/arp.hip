@@ -4,20 +4,21 @@
 // read in place.  The per-lane steps are arp_lane.hip.h; semantics and what is defined where the reference is not: zang_hip.h.
 #include "common.hip.h"
 #include "arp_lane.hip.h"
+#include "span_stage.hip.h"
 #include <vector>
 #include <string.h>
 
 namespace {
 constexpr uint32_t kArpBlock = 64;
 constexpr uint32_t kArpDefaultRows = 4;
+static_assert(ZH_ARP_SPAN_FREQ == 0 && ZH_ARP_SPAN_NOTE_ON == 1 && ZH_ARP_SPAN_FIELDS == 2, "the fields StageWriter emits");
 
 struct ArpArgs {
     uint32_t n, n_keys, nd, out_len, in_spans, max_spans;
     const uint32_t *key_freq_bits;                                    // [n_keys]
     const uint32_t *in_count, *in_start, *in_end, *held_lo, *held_hi; // the outer table, [in_spans][n]
     uint32_t *state;                                                  // [kArpState][n]
-    uint32_t *count, *start, *end, *freq, *note_on;                   // the stage's table, [rows][n]
-    uint8_t *changed;
+    StageRows out;                                                    // the stage's table: fields ZH_ARP_SPAN_FREQ, _NOTE_ON
     uint32_t *overflow;
 };
 
@@ -28,48 +29,23 @@ __global__ void __launch_bounds__(kArpBlock) k_arp_schedule(const ArpArgs a) {
     ArpLane s;
     arp_load(s, a.state, n, p);
     const uint32_t cnt = min(a.in_count[p], a.in_spans);
-    uint32_t k = 0, dropped = 0;
-    arp_buffer(s, a.key_freq_bits, a.n_keys, a.nd, a.out_len, cnt, a.in_start + p, a.in_end + p, a.held_lo + p, a.held_hi + p, n,
-               [&](uint32_t s0, uint32_t s1, uint32_t freq_bits, uint32_t note_on, uint32_t changed) {
-        if (k >= a.max_spans) { dropped++; return; }
-        const size_t idx = (size_t)k * n + p;
-        a.start[idx] = s0; a.end[idx] = s1; a.freq[idx] = freq_bits; a.note_on[idx] = note_on; a.changed[idx] = (uint8_t)changed;
-        k++;
-    });
-    a.count[p] = k;
+    StageWriter emit{a.out, n, p, a.max_spans, 0, 0};
+    arp_buffer(s, a.key_freq_bits, a.n_keys, a.nd, a.out_len, cnt, a.in_start + p, a.in_end + p, a.held_lo + p, a.held_hi + p, n, emit);
+    a.out.count[p] = emit.k;
     arp_store(s, a.state, n, p);
-    if (dropped) atomicAdd(a.overflow, dropped);
+    if (emit.dropped) atomicAdd(a.overflow, emit.dropped);
 }
 }  // namespace
 
-struct zh_arp {
-    zh_ctx *ctx;
-    uint32_t n, n_keys, rows;
+struct zh_arp : zh_stage {
+    uint32_t n, n_keys;
     uint32_t *key_freq_bits, *state;
-    uint32_t *count, *start, *end, *freq, *note_on;
-    uint8_t *changed;
-    uint32_t *overflow;
 };
 
 namespace {
-void arp_free_tables(zh_arp *a) {
-    (void)hipFree(a->start); (void)hipFree(a->end); (void)hipFree(a->freq); (void)hipFree(a->note_on); (void)hipFree(a->changed);
-    a->start = a->end = a->freq = a->note_on = nullptr; a->changed = nullptr; a->rows = 0;
-}
 void arp_free(zh_arp *a) {
-    arp_free_tables(a);
-    (void)hipFree(a->key_freq_bits); (void)hipFree(a->state); (void)hipFree(a->count); (void)hipFree(a->overflow);
-}
-int arp_alloc_tables(zh_arp *a, uint32_t rows) {
-    const size_t cells = (size_t)rows * a->n;
-    int rc = dev_alloc(&a->start, cells);
-    if (!rc) rc = dev_alloc(&a->end, cells);
-    if (!rc) rc = dev_alloc(&a->freq, cells);
-    if (!rc) rc = dev_alloc(&a->note_on, cells);
-    if (!rc) rc = dev_alloc(&a->changed, cells);
-    if (rc) { arp_free_tables(a); (void)hipGetLastError(); return rc; }
-    a->rows = rows;
-    return ZH_OK;
+    stage_free(a->tab);
+    (void)hipFree(a->key_freq_bits); (void)hipFree(a->state);
 }
 void arp_pack(const zh_arp_state &h, uint32_t *w, size_t n, size_t v) {
     uint32_t fb;
@@ -98,25 +74,15 @@ int zh_arp_create(zh_ctx *ctx, uint32_t n_players, const float *key_freqs, uint3
     a->ctx = ctx; a->n = n_players; a->n_keys = n_keys;
     int rc = dev_alloc(&a->key_freq_bits, (size_t)n_keys);
     if (!rc) rc = dev_alloc(&a->state, (size_t)kArpState * n_players);
-    if (!rc) rc = dev_alloc(&a->count, (size_t)n_players);
-    if (!rc) rc = dev_alloc(&a->overflow, 1);
-    if (!rc) rc = arp_alloc_tables(a, kArpDefaultRows);
-    if (!rc) rc = (int)hipMemsetAsync(a->overflow, 0, 4, ctx->stream);
-    if (!rc && n_players) rc = (int)hipMemsetAsync(a->count, 0, (size_t)n_players * 4, ctx->stream);
+    if (!rc) rc = stage_create(a, n_players, ZH_ARP_SPAN_FIELDS, kArpDefaultRows);
     if (!rc) rc = zh_upload(ctx, a->key_freq_bits, key_freqs, (size_t)n_keys * 4);
     if (!rc) rc = arp_upload_init(a);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); arp_free(a); delete a; (void)hipGetLastError(); return rc; }
+    if (rc) return stage_create_failed(a, arp_free, rc);
     *out = a;
     return ZH_OK;
 }
 
-int zh_arp_destroy(zh_arp *a) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a) return ZH_ERR_INVALID;
-    if (!a->ctx->capturing) (void)hipStreamSynchronize(a->ctx->stream);
-    arp_free(a);
-    delete a;
-    return ZH_OK;
-}
+int zh_arp_destroy(zh_arp *a) { ZH_GUARD(a ? a->ctx : nullptr); return stage_destroy(a, arp_free); }
 
 int zh_arp_reset(zh_arp *a) { ZH_GUARD(a ? a->ctx : nullptr);
     if (!a) return ZH_ERR_INVALID;
@@ -124,46 +90,25 @@ int zh_arp_reset(zh_arp *a) { ZH_GUARD(a ? a->ctx : nullptr);
     return arp_upload_init(a);
 }
 
-int zh_arp_reserve(zh_arp *a, uint32_t max_rows) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a || max_rows == 0) return ZH_ERR_INVALID;
-    if (a->ctx->capturing) return ZH_ERR_UNSUPPORTED;
-    if (max_rows == a->rows) return ZH_OK;
-    ZH_TRY(hipStreamSynchronize(a->ctx->stream));
-    arp_free_tables(a);
-    return arp_alloc_tables(a, max_rows);
-}
+int zh_arp_reserve(zh_arp *a, uint32_t max_rows) { ZH_GUARD(a ? a->ctx : nullptr); return stage_reserve(a, max_rows); }
 
 int zh_arp_schedule(zh_arp *a, float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table *in,
                     const zh_script_span_param *held) { ZH_GUARD(a ? a->ctx : nullptr);
     uint32_t nd = 0;
-    if (!a || !in || !held || max_spans == 0 || max_spans > a->rows || in->max_spans == 0 || !in->count || !in->start || !in->end ||
-        !held[0].u || !held[1].u || !arp_note_duration(sample_rate, nd))
+    if (!stage_spans_ok(a, max_spans) || !stage_input_ok(in, false) || !held || !held[0].u || !held[1].u || !arp_note_duration(sample_rate, nd))
         return ZH_ERR_INVALID;
     if (a->n == 0) return ZH_OK;
     const ArpArgs args{a->n, a->n_keys, nd, out_len, in->max_spans, max_spans, a->key_freq_bits, in->count, in->start, in->end,
-                       held[0].u, held[1].u, a->state, a->count, a->start, a->end, a->freq, a->note_on, a->changed, a->overflow};
+                       held[0].u, held[1].u, a->state, stage_rows(a), a->tab.overflow};
     ZH_LAUNCH(k_arp_schedule, dim3((a->n + kArpBlock - 1) / kArpBlock), dim3(kArpBlock), 0, a->ctx->stream, args);
     return zh_launch_status();
 }
 
-int zh_arp_script_table(const zh_arp *a, uint32_t max_spans, zh_script_span_table *out) {
-    if (!a || !out || max_spans == 0 || max_spans > a->rows) return ZH_ERR_INVALID;
-    *out = zh_script_span_table{max_spans, 0, a->count, a->start, a->end, a->changed};
-    return ZH_OK;
-}
+int zh_arp_script_table(const zh_arp *a, uint32_t max_spans, zh_script_span_table *out) { return stage_script_table(a, max_spans, out); }
 int zh_arp_span_param(const zh_arp *a, uint32_t field, zh_script_span_param *out) {
-    if (!a || !out || field >= ZH_ARP_SPAN_FIELDS) return ZH_ERR_INVALID;
-    *out = field == ZH_ARP_SPAN_FREQ ? zh_script_span_param{(const float *)a->freq, nullptr} : zh_script_span_param{nullptr, a->note_on};
-    return ZH_OK;
+    return stage_span_param(a, field, field == ZH_ARP_SPAN_FREQ ? 'f' : 'u', out);
 }
-
-int zh_arp_overflows(zh_arp *a, uint64_t *out) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a || !out) return ZH_ERR_INVALID;
-    uint32_t w = 0;
-    int rc = zh_download(a->ctx, &w, a->overflow, 4);
-    *out = w;
-    return rc;
-}
+int zh_arp_overflows(zh_arp *a, uint64_t *out) { ZH_GUARD(a ? a->ctx : nullptr); return stage_overflows(a, out); }
 
 int zh_arp_get_state(zh_arp *a, zh_arp_state *host) { ZH_GUARD(a ? a->ctx : nullptr);
     if (!a || (a->n && !host)) return ZH_ERR_INVALID;

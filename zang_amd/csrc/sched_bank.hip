@@ -13,6 +13,7 @@
 // are adjacent voices, so every store is a coalesced row segment.  Buffers loop A, B inside the launch.
 #include "common.hip.h"
 #include "sched_lane.hip.h"
+#include "span_stage.hip.h"
 #include <string.h>
 #include <vector>
 
@@ -178,15 +179,13 @@ __global__ void __launch_bounds__(kBankBlock) k_voice_bank_schedule_live(LiveArg
 }
 }  // namespace
 
-struct zh_voice_bank {
-    zh_ctx *ctx;
-    uint32_t n, P, words, note_on_offset, ipb, rows;
+struct zh_voice_bank : zh_stage {                 // tab: rows of n * P voices, one field per record word
+    uint32_t n, P, words, note_on_offset, ipb;
     uint64_t n_events;
     float *t; uint64_t *note_id; uint32_t *rec, *offsets;
     uint32_t *next; float *clock;
     uint32_t *slot_flags, *trig_has, *trig_ev; uint64_t *slot_note, *slot_event, *trig_note;
-    uint32_t *count, *start, *end, *wordsbuf; uint8_t *note_on, *changed;
-    uint32_t *overflow;
+    uint8_t *note_on;                             // [rows][n * P], beside the table's rows
     // a live bank (zh_voice_bank_create_live): no song, no tracker; per call one batch of pushed impulses
     bool live;
     uint32_t max_impulses;
@@ -202,31 +201,23 @@ namespace {
 // a batch of m impulses as ONE block: u64 note_id[m], u32 offsets[n + 1], u32 frame[m], u32 rec[m][words]
 size_t bank_batch_bytes(const zh_voice_bank *b, size_t m) { return m * 8 + ((size_t)b->n + 1) * 4 + m * 4 + m * 4 * b->words; }
 size_t bank_voices(const zh_voice_bank *b) { return (size_t)b->n * b->P; }
-void bank_free_tables(zh_voice_bank *b) {
-    (void)hipFree(b->start); (void)hipFree(b->end); (void)hipFree(b->wordsbuf); (void)hipFree(b->note_on); (void)hipFree(b->changed);
-    b->start = b->end = b->wordsbuf = nullptr; b->note_on = b->changed = nullptr; b->rows = 0;
-}
 void bank_free(zh_voice_bank *b) {
-    bank_free_tables(b);
+    stage_free(b->tab);
+    (void)hipFree(b->note_on);
     (void)hipFree(b->t); (void)hipFree(b->note_id); (void)hipFree(b->rec); (void)hipFree(b->offsets); (void)hipFree(b->next); (void)hipFree(b->clock);
     (void)hipFree(b->slot_flags); (void)hipFree(b->trig_has); (void)hipFree(b->trig_ev); (void)hipFree(b->slot_note); (void)hipFree(b->slot_event);
-    (void)hipFree(b->trig_note); (void)hipFree(b->count); (void)hipFree(b->overflow);
+    (void)hipFree(b->trig_note);
     (void)hipFree(b->next_event_id); (void)hipFree(b->carried); (void)hipFree(b->batch);
     for (uint32_t k = 0; k < kBankStageSlots; k++) {
         if (b->stage[k]) (void)hipHostFree(b->stage[k]);
         if (b->stage_done[k]) (void)hipEventDestroy(b->stage_done[k]);
     }
 }
-int bank_alloc_tables(zh_voice_bank *b, uint32_t rows) {
-    const size_t cells = (size_t)rows * bank_voices(b);
-    int rc = dev_alloc(&b->start, cells);
-    if (!rc) rc = dev_alloc(&b->end, cells);
-    if (!rc) rc = dev_alloc(&b->wordsbuf, cells * b->words);
-    if (!rc) rc = dev_alloc(&b->note_on, cells);
-    if (!rc) rc = dev_alloc(&b->changed, cells);
-    if (rc) { bank_free_tables(b); (void)hipGetLastError(); return rc; }
-    b->rows = rows;
-    return ZH_OK;
+// the table with kBankDefaultRows rows and the note_on plane beside it
+int bank_create_tables(zh_voice_bank *b) {
+    int rc = stage_create(b, (uint32_t)bank_voices(b), b->words, kBankDefaultRows);
+    if (!rc) rc = dev_alloc(&b->note_on, kBankDefaultRows * bank_voices(b));
+    return rc;
 }
 int bank_clear_state(zh_voice_bank *b) {                          // example_song.zig:318-324 (and Trigger.init / NoteTracker.init)
     const size_t nv = bank_voices(b);
@@ -283,11 +274,7 @@ int zh_voice_bank_create(zh_ctx *ctx, uint32_t n_instruments, uint32_t polyphony
     if (!rc) rc = dev_alloc(&b->trig_has, nv);
     if (!rc) rc = dev_alloc(&b->trig_ev, nv);
     if (!rc) rc = dev_alloc(&b->trig_note, nv);
-    if (!rc) rc = dev_alloc(&b->count, nv);
-    if (!rc) rc = dev_alloc(&b->overflow, 1);
-    if (!rc) rc = bank_alloc_tables(b, kBankDefaultRows);
-    if (!rc) rc = (int)hipMemsetAsync(b->overflow, 0, 4, ctx->stream);
-    if (!rc && nv) rc = (int)hipMemsetAsync(b->count, 0, nv * 4, ctx->stream);
+    if (!rc) rc = bank_create_tables(b);
     if (!rc) rc = bank_clear_state(b);
     if (!rc && n_events) {
         rc = zh_upload(ctx, b->t, t, n_events * 4);
@@ -299,18 +286,12 @@ int zh_voice_bank_create(zh_ctx *ctx, uint32_t n_instruments, uint32_t polyphony
         for (uint32_t i = 0; i <= n_instruments; i++) off[i] = (uint32_t)event_offsets[i];
         rc = zh_upload(ctx, b->offsets, off.data(), off.size() * 4);
     }
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); bank_free(b); delete b; (void)hipGetLastError(); return rc; }
+    if (rc) return stage_create_failed(b, bank_free, rc);
     *out = b;
     return ZH_OK;
 }
 
-int zh_voice_bank_destroy(zh_voice_bank *b) { ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b) return ZH_ERR_INVALID;
-    if (!b->ctx->capturing) (void)hipStreamSynchronize(b->ctx->stream);
-    bank_free(b);
-    delete b;
-    return ZH_OK;
-}
+int zh_voice_bank_destroy(zh_voice_bank *b) { ZH_GUARD(b ? b->ctx : nullptr); return stage_destroy(b, bank_free); }
 
 int zh_voice_bank_reset(zh_voice_bank *b) { ZH_GUARD(b ? b->ctx : nullptr);
     if (!b) return ZH_ERR_INVALID;
@@ -318,31 +299,33 @@ int zh_voice_bank_reset(zh_voice_bank *b) { ZH_GUARD(b ? b->ctx : nullptr);
 }
 
 int zh_voice_bank_reserve(zh_voice_bank *b, uint32_t max_rows) { ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || max_rows == 0) return ZH_ERR_INVALID;
-    if (b->ctx->capturing) return ZH_ERR_UNSUPPORTED;
-    if (max_rows == b->rows) return ZH_OK;
-    ZH_TRY(hipStreamSynchronize(b->ctx->stream));
-    bank_free_tables(b);
-    return bank_alloc_tables(b, max_rows);
+    const uint32_t had = b ? b->tab.rows : 0;
+    int rc = stage_reserve(b, max_rows);
+    if (rc || b->tab.rows == had) return rc;                      // refused, or the same capacity
+    (void)hipFree(b->note_on);                                    // (the stream is idle: stage_reserve)
+    rc = dev_alloc(&b->note_on, (size_t)max_rows * bank_voices(b));
+    if (rc) { stage_free_rows(b->tab); (void)hipGetLastError(); }
+    return rc;
 }
 
 int zh_voice_bank_schedule(zh_voice_bank *b, float sample_rate, const uint32_t *frames, uint32_t n_buffers, uint32_t max_spans) {
     ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || b->live || (n_buffers && !frames) || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
+    if (!stage_spans_ok(b, max_spans) || b->live || (n_buffers && !frames)) return ZH_ERR_INVALID;
     uint64_t total = 0;
     for (uint32_t i = 0; i < n_buffers; i++) total += frames[i];
     if (total >> 32) return ZH_ERR_INVALID;
     if (b->n == 0) return ZH_OK;
     hipStream_t st = b->ctx->stream;
-    if (n_buffers == 0) { ZH_TRY(hipMemsetAsync(b->count, 0, bank_voices(b) * 4, st)); return ZH_OK; }
+    const StageRows rows = stage_rows(b);
+    if (n_buffers == 0) { ZH_TRY(hipMemsetAsync(rows.count, 0, bank_voices(b) * 4, st)); return ZH_OK; }
     BankArgs a;
     a.song = ZsSong{b->t, b->note_id, b->rec, b->words, b->note_on_offset / 4, (b->note_on_offset & 3u) * 8};
     a.offsets = b->offsets; a.n = b->n; a.P = b->P; a.ipb = b->ipb;
     a.next = b->next; a.t = b->clock;
     a.slot_flags = b->slot_flags; a.slot_note = b->slot_note; a.slot_event = b->slot_event;
     a.trig_has = b->trig_has; a.trig_ev = b->trig_ev; a.trig_note = b->trig_note;
-    a.count = b->count; a.start = b->start; a.end = b->end; a.words = b->wordsbuf; a.note_on = b->note_on; a.changed = b->changed;
-    a.plane = (size_t)b->rows * bank_voices(b); a.max_spans = max_spans; a.overflow = b->overflow;
+    a.count = rows.count; a.start = rows.start; a.end = rows.end; a.words = rows.words; a.note_on = b->note_on; a.changed = rows.changed;
+    a.plane = rows.plane; a.max_spans = max_spans; a.overflow = b->tab.overflow;
     const dim3 grid((b->n + b->ipb - 1) / b->ipb);
     const size_t lds = bank_lds_bytes(b->ipb, b->P);
     BankFrames fr;
@@ -357,31 +340,16 @@ int zh_voice_bank_schedule(zh_voice_bank *b, float sample_rate, const uint32_t *
     return zh_launch_status();
 }
 
-int zh_voice_bank_script_table(const zh_voice_bank *b, uint32_t max_spans, zh_script_span_table *out) {
-    if (!b || !out || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
-    *out = zh_script_span_table{max_spans, 0, b->count, b->start, b->end, b->changed};
-    return ZH_OK;
-}
-int zh_voice_bank_span_param(const zh_voice_bank *b, uint32_t word, zh_script_span_param *out) {
-    if (!b || !out || word >= b->words) return ZH_ERR_INVALID;
-    const uint32_t *p = b->wordsbuf + (size_t)word * b->rows * bank_voices(b);
-    *out = zh_script_span_param{(const float *)p, p};
-    return ZH_OK;
-}
+int zh_voice_bank_script_table(const zh_voice_bank *b, uint32_t max_spans, zh_script_span_table *out) { return stage_script_table(b, max_spans, out); }
+int zh_voice_bank_span_param(const zh_voice_bank *b, uint32_t word, zh_script_span_param *out) { return stage_span_param(b, word, 0, out); }
 int zh_voice_bank_span_table(const zh_voice_bank *b, uint32_t max_spans, uint32_t freq_word, zh_span_table *out) {
-    if (!b || !out || max_spans == 0 || max_spans > b->rows || freq_word >= b->words) return ZH_ERR_INVALID;
-    const uint32_t *p = b->wordsbuf + (size_t)freq_word * b->rows * bank_voices(b);
-    *out = zh_span_table{max_spans, 0, b->count, b->start, b->end, (const float *)p, b->note_on, b->changed};
+    zh_script_span_table t;
+    zh_script_span_param freq;
+    if (!out || stage_script_table(b, max_spans, &t) || stage_span_param(b, freq_word, 'f', &freq)) return ZH_ERR_INVALID;
+    *out = zh_span_table{max_spans, 0, t.count, t.start, t.end, freq.f, b->note_on, t.note_id_changed};
     return ZH_OK;
 }
-
-int zh_voice_bank_overflows(zh_voice_bank *b, uint64_t *out) { ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || !out) return ZH_ERR_INVALID;
-    uint32_t w = 0;
-    int rc = zh_download(b->ctx, &w, b->overflow, 4);
-    *out = w;
-    return rc;
-}
+int zh_voice_bank_overflows(zh_voice_bank *b, uint64_t *out) { ZH_GUARD(b ? b->ctx : nullptr); return stage_overflows(b, out); }
 
 int zh_voice_bank_get_state(zh_voice_bank *b, zh_voice_bank_instrument_state *instruments, zh_voice_bank_voice_state *voices) {
     ZH_GUARD(b ? b->ctx : nullptr);
@@ -460,30 +428,26 @@ int zh_voice_bank_create_live(zh_ctx *ctx, uint32_t n_instruments, uint32_t poly
     if (!rc) rc = dev_alloc(&b->trig_has, nv);
     if (!rc) rc = dev_alloc(&b->trig_note, nv);
     if (!rc) rc = dev_alloc(&b->carried, nv * b->words);
-    if (!rc) rc = dev_alloc(&b->count, nv);
-    if (!rc) rc = dev_alloc(&b->overflow, 1);
     if (!rc && n_instruments) rc = dev_alloc(&b->batch, bytes);
     for (uint32_t k = 0; !rc && n_instruments && k < kBankStageSlots; k++) {
         rc = (int)hipHostMalloc((void **)&b->stage[k], bytes, hipHostMallocDefault);
         if (!rc) rc = (int)hipEventCreateWithFlags(&b->stage_done[k], hipEventDisableTiming);
     }
-    if (!rc) rc = bank_alloc_tables(b, kBankDefaultRows);
-    if (!rc) rc = (int)hipMemsetAsync(b->overflow, 0, 4, ctx->stream);
-    if (!rc && nv) rc = (int)hipMemsetAsync(b->count, 0, nv * 4, ctx->stream);
+    if (!rc) rc = bank_create_tables(b);
     if (!rc && nv) rc = (int)hipMemsetAsync(b->carried, 0, nv * b->words * 4, ctx->stream);
     if (!rc) rc = bank_clear_state(b);
     if (!rc && n_instruments) {                                                    // ImpulseQueue.init: next_event_id = 1
         const std::vector<uint64_t> ones(n_instruments, 1);
         rc = zh_upload(ctx, b->next_event_id, ones.data(), (size_t)n_instruments * 8);
     }
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); bank_free(b); delete b; (void)hipGetLastError(); return rc; }
+    if (rc) return stage_create_failed(b, bank_free, rc);
     *out = b;
     return ZH_OK;
 }
 
 int zh_voice_bank_schedule_live(zh_voice_bank *b, uint32_t out_len, uint32_t max_spans, const zh_bank_impulses *batch) {
     ZH_GUARD(b ? b->ctx : nullptr);
-    if (!b || !b->live || max_spans == 0 || max_spans > b->rows) return ZH_ERR_INVALID;
+    if (!stage_spans_ok(b, max_spans) || !b->live) return ZH_ERR_INVALID;
     const uint32_t m = batch ? batch->n : 0u;
     if (m > b->max_impulses || (m && (!batch->instrument || !batch->frame || !batch->note_id || !batch->paramses))) return ZH_ERR_INVALID;
     for (uint32_t i = 0; i < m; i++) if (batch->instrument[i] >= b->n) return ZH_ERR_INVALID;
@@ -519,8 +483,9 @@ int zh_voice_bank_schedule_live(zh_voice_bank *b, uint32_t out_len, uint32_t max
     a.next_event_id = b->next_event_id;
     a.slot_flags = b->slot_flags; a.slot_note = b->slot_note; a.slot_event = b->slot_event;
     a.trig_has = b->trig_has; a.trig_note = b->trig_note; a.carried = b->carried;
-    a.count = b->count; a.start = b->start; a.end = b->end; a.words = b->wordsbuf; a.note_on = b->note_on; a.changed = b->changed;
-    a.plane = (size_t)b->rows * bank_voices(b); a.max_spans = max_spans; a.overflow = b->overflow;
+    const StageRows rows = stage_rows(b);
+    a.count = rows.count; a.start = rows.start; a.end = rows.end; a.words = rows.words; a.note_on = b->note_on; a.changed = rows.changed;
+    a.plane = rows.plane; a.max_spans = max_spans; a.overflow = b->tab.overflow;
     ZH_LAUNCH(k_voice_bank_schedule_live, dim3((b->n + b->ipb - 1) / b->ipb), dim3(kBankBlock), bank_lds_bytes(b->ipb, b->P), st, a, out_len);
     return zh_launch_status();
 }

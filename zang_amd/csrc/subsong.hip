@@ -6,6 +6,7 @@
 // zang_hip.h.
 #include "common.hip.h"
 #include "subsong_lane.hip.h"
+#include "span_stage.hip.h"
 #include <vector>
 #include <string.h>
 
@@ -13,6 +14,7 @@ namespace {
 constexpr uint32_t kSubsongBlock = 64;
 constexpr uint32_t kSubsongDefaultRows = 33;                          // what one outer sub-span can make: the carried note + 32 impulses
 static_assert(kSubsongNoMelody == UINT32_MAX, "the value zang_hip.h documents");
+static_assert(ZH_SUBSONG_SPAN_FREQ == 0 && ZH_SUBSONG_SPAN_NOTE_ON == 1 && ZH_SUBSONG_SPAN_FIELDS == 2, "the fields StageWriter emits");
 
 struct SubsongArgs {
     uint32_t n, out_len, in_spans, max_spans;
@@ -23,8 +25,7 @@ struct SubsongArgs {
     const float *in_freq;
     const uint32_t *in_note_on, *in_melody;
     uint32_t *state;                                                  // [kSubsongState][n]
-    uint32_t *count, *start, *end, *freq, *note_on;                   // the stage's table, [rows][n]
-    uint8_t *changed;
+    StageRows out;                                                    // the stage's table: fields ZH_SUBSONG_SPAN_FREQ, _NOTE_ON
     uint32_t *overflow;
 };
 
@@ -35,10 +36,10 @@ __global__ void __launch_bounds__(kSubsongBlock) k_subsong_schedule(const Subson
     SubsongLane s;
     subsong_load(s, a.state, n, p);
     const uint32_t cnt = min(a.in_count[p], a.in_spans);
-    SubsongEmit emit{SubsongRowsP{a.start, a.end, a.freq, a.note_on, a.changed}, n, p, a.max_spans, 0, 0};
+    StageWriter emit{a.out, n, p, a.max_spans, 0, 0};
     subsong_buffer(s, a.kit, a.base_freq, a.sample_rate, a.out_len, cnt, a.in_start + p, a.in_end + p, a.in_nic + p, a.in_freq + p,
                    a.in_note_on + p, a.in_melody + p, n, emit);
-    a.count[p] = emit.k;
+    a.out.count[p] = emit.k;
     subsong_store(s, a.state, n, p);
     if (emit.dropped) atomicAdd(a.overflow, emit.dropped);
 }
@@ -51,36 +52,17 @@ struct zh_melody_kit {
     SubsongKitP p;
 };
 
-struct zh_subsong {
-    zh_ctx *ctx;
+struct zh_subsong : zh_stage {
     const zh_melody_kit *kit;
-    uint32_t n, rows;
+    uint32_t n;
     float base_freq;
     uint32_t *state;
-    uint32_t *count, *start, *end, *freq, *note_on;
-    uint8_t *changed;
-    uint32_t *overflow;
 };
 
 namespace {
-void subsong_free_tables(zh_subsong *a) {
-    (void)hipFree(a->start); (void)hipFree(a->end); (void)hipFree(a->freq); (void)hipFree(a->note_on); (void)hipFree(a->changed);
-    a->start = a->end = a->freq = a->note_on = nullptr; a->changed = nullptr; a->rows = 0;
-}
 void subsong_free(zh_subsong *a) {
-    subsong_free_tables(a);
-    (void)hipFree(a->state); (void)hipFree(a->count); (void)hipFree(a->overflow);
-}
-int subsong_alloc_tables(zh_subsong *a, uint32_t rows) {
-    const size_t cells = (size_t)rows * a->n;
-    int rc = dev_alloc(&a->start, cells);
-    if (!rc) rc = dev_alloc(&a->end, cells);
-    if (!rc) rc = dev_alloc(&a->freq, cells);
-    if (!rc) rc = dev_alloc(&a->note_on, cells);
-    if (!rc) rc = dev_alloc(&a->changed, cells);
-    if (rc) { subsong_free_tables(a); (void)hipGetLastError(); return rc; }
-    a->rows = rows;
-    return ZH_OK;
+    stage_free(a->tab);
+    (void)hipFree(a->state);
 }
 int subsong_upload_init(zh_subsong *a) {                              // init() :104-120
     if (!a->n) return ZH_OK;
@@ -153,24 +135,14 @@ int zh_subsong_create(zh_ctx *ctx, uint32_t n_players, const zh_melody_kit *kit,
     memset(a, 0, sizeof *a);
     a->ctx = ctx; a->kit = kit; a->n = n_players; a->base_freq = base_freq;
     int rc = dev_alloc(&a->state, (size_t)kSubsongState * n_players);
-    if (!rc) rc = dev_alloc(&a->count, (size_t)n_players);
-    if (!rc) rc = dev_alloc(&a->overflow, 1);
-    if (!rc) rc = subsong_alloc_tables(a, kSubsongDefaultRows);
-    if (!rc) rc = (int)hipMemsetAsync(a->overflow, 0, 4, ctx->stream);
-    if (!rc && n_players) rc = (int)hipMemsetAsync(a->count, 0, (size_t)n_players * 4, ctx->stream);
+    if (!rc) rc = stage_create(a, n_players, ZH_SUBSONG_SPAN_FIELDS, kSubsongDefaultRows);
     if (!rc) rc = subsong_upload_init(a);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); subsong_free(a); delete a; (void)hipGetLastError(); return rc; }
+    if (rc) return stage_create_failed(a, subsong_free, rc);
     *out = a;
     return ZH_OK;
 }
 
-int zh_subsong_destroy(zh_subsong *a) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a) return ZH_ERR_INVALID;
-    if (!a->ctx->capturing) (void)hipStreamSynchronize(a->ctx->stream);
-    subsong_free(a);
-    delete a;
-    return ZH_OK;
-}
+int zh_subsong_destroy(zh_subsong *a) { ZH_GUARD(a ? a->ctx : nullptr); return stage_destroy(a, subsong_free); }
 
 int zh_subsong_reset(zh_subsong *a) { ZH_GUARD(a ? a->ctx : nullptr);
     if (!a) return ZH_ERR_INVALID;
@@ -178,46 +150,26 @@ int zh_subsong_reset(zh_subsong *a) { ZH_GUARD(a ? a->ctx : nullptr);
     return subsong_upload_init(a);
 }
 
-int zh_subsong_reserve(zh_subsong *a, uint32_t max_rows) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a || max_rows == 0) return ZH_ERR_INVALID;
-    if (a->ctx->capturing) return ZH_ERR_UNSUPPORTED;
-    if (max_rows == a->rows) return ZH_OK;
-    ZH_TRY(hipStreamSynchronize(a->ctx->stream));
-    subsong_free_tables(a);
-    return subsong_alloc_tables(a, max_rows);
-}
+int zh_subsong_reserve(zh_subsong *a, uint32_t max_rows) { ZH_GUARD(a ? a->ctx : nullptr); return stage_reserve(a, max_rows); }
 
 int zh_subsong_schedule(zh_subsong *a, float sample_rate, uint32_t out_len, uint32_t max_spans, const zh_script_span_table *in,
                         const zh_script_span_param *outer) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a || !in || !outer || max_spans == 0 || max_spans > a->rows || in->max_spans == 0 || !in->count || !in->start || !in->end ||
-        !in->note_id_changed || !outer[ZH_SUBSONG_IN_FREQ].f || !outer[ZH_SUBSONG_IN_NOTE_ON].u || !outer[ZH_SUBSONG_IN_MELODY].u)
+    if (!stage_spans_ok(a, max_spans) || !stage_input_ok(in, true) || !outer || !outer[ZH_SUBSONG_IN_FREQ].f ||
+        !outer[ZH_SUBSONG_IN_NOTE_ON].u || !outer[ZH_SUBSONG_IN_MELODY].u)
         return ZH_ERR_INVALID;
     if (a->n == 0) return ZH_OK;
     const SubsongArgs args{a->n, out_len, in->max_spans, max_spans, sample_rate, a->base_freq, a->kit->p, in->count, in->start, in->end,
                            in->note_id_changed, outer[ZH_SUBSONG_IN_FREQ].f, outer[ZH_SUBSONG_IN_NOTE_ON].u, outer[ZH_SUBSONG_IN_MELODY].u,
-                           a->state, a->count, a->start, a->end, a->freq, a->note_on, a->changed, a->overflow};
+                           a->state, stage_rows(a), a->tab.overflow};
     ZH_LAUNCH(k_subsong_schedule, dim3((a->n + kSubsongBlock - 1) / kSubsongBlock), dim3(kSubsongBlock), 0, a->ctx->stream, args);
     return zh_launch_status();
 }
 
-int zh_subsong_script_table(const zh_subsong *a, uint32_t max_spans, zh_script_span_table *out) {
-    if (!a || !out || max_spans == 0 || max_spans > a->rows) return ZH_ERR_INVALID;
-    *out = zh_script_span_table{max_spans, 0, a->count, a->start, a->end, a->changed};
-    return ZH_OK;
-}
+int zh_subsong_script_table(const zh_subsong *a, uint32_t max_spans, zh_script_span_table *out) { return stage_script_table(a, max_spans, out); }
 int zh_subsong_span_param(const zh_subsong *a, uint32_t field, zh_script_span_param *out) {
-    if (!a || !out || field >= ZH_SUBSONG_SPAN_FIELDS) return ZH_ERR_INVALID;
-    *out = field == ZH_SUBSONG_SPAN_FREQ ? zh_script_span_param{(const float *)a->freq, nullptr} : zh_script_span_param{nullptr, a->note_on};
-    return ZH_OK;
+    return stage_span_param(a, field, field == ZH_SUBSONG_SPAN_FREQ ? 'f' : 'u', out);
 }
-
-int zh_subsong_overflows(zh_subsong *a, uint64_t *out) { ZH_GUARD(a ? a->ctx : nullptr);
-    if (!a || !out) return ZH_ERR_INVALID;
-    uint32_t w = 0;
-    int rc = zh_download(a->ctx, &w, a->overflow, 4);
-    *out = w;
-    return rc;
-}
+int zh_subsong_overflows(zh_subsong *a, uint64_t *out) { ZH_GUARD(a ? a->ctx : nullptr); return stage_overflows(a, out); }
 
 int zh_subsong_get_state(zh_subsong *a, zh_subsong_state *host) { ZH_GUARD(a ? a->ctx : nullptr);
     if (!a || (a->n && !host)) return ZH_ERR_INVALID;

@@ -7,14 +7,8 @@
 // whose t is not below end_t; impulse i of the call is event first + i, and its frame is a function of that event's t and of the
 // clock before the call (subsong frame_of), evaluated where the walk asks for it.  f32 throughout, no contraction.
 #pragma once
-#include <stdint.h>
-#include <stddef.h>
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define SS_HD __host__ __device__ inline
-#else
-#define SS_HD inline
-#endif
+#include "span_stage.hip.h"
+#define SS_HD STAGE_HD
 
 constexpr uint32_t kSubsongMaxImpulses = 32;     // NoteTracker's arrays (notes.zig:142-143)
 constexpr uint32_t kSubsongNoMelody = 0xffffffffu;   // the latched melody of a player that plays none (an index at or above K)
@@ -72,23 +66,15 @@ SS_HD void subsong_store(const SubsongLane &s, uint32_t *w, size_t n, size_t v) 
     put(SS_NOTE_ON, s.note_on);
 }
 
-// The stage's own table, [row][player], and what takes one player's rows into it: row k of player p at k * n + p; a player's list
-// stops at max_spans, what does not fit is counted.  The kernel and the CPU harness both emit through it.
+// The stage's table as five arrays of their own, [row][player] (the CPU harness's), under the writer the kernel emits through
 struct SubsongRowsP {
     uint32_t *start, *end, *freq, *note_on;
     uint8_t *changed;
-};
-struct SubsongEmit {
-    SubsongRowsP rows;
-    size_t n, p;
-    uint32_t max_spans, k, dropped;
-    SS_HD void operator()(uint32_t s0, uint32_t s1, uint32_t freq_bits, uint32_t note_on, uint32_t changed) {
-        if (k >= max_spans) { dropped++; return; }
-        const size_t idx = (size_t)k * n + p;
-        rows.start[idx] = s0; rows.end[idx] = s1; rows.freq[idx] = freq_bits; rows.note_on[idx] = note_on; rows.changed[idx] = (uint8_t)changed;
-        k++;
+    SS_HD void freq_on(size_t idx, uint32_t freq_bits, uint32_t on, uint32_t nic) const {
+        freq[idx] = freq_bits; note_on[idx] = on; changed[idx] = (uint8_t)nic;
     }
 };
+using SubsongEmit = StageWriterT<SubsongRowsP>;
 
 // One SubtrackPlayer.paint call: outer sub-span [start, end), start < end, with the outer note's freq, note_on, note_id_changed
 // and melody.  emit(sub_start, sub_end, freq_bits, note_on, note_id_changed) per inner sub-span, in order.

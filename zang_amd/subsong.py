@@ -9,6 +9,7 @@ import numpy as np
 
 from . import abi, modules as mod, zang
 from .bank import LiveVoiceBank
+from .stage import Stage, StageTable
 
 # the outer record: SubtrackPlayer.Params (:92-96) without the shared sample rate, and which of the kit's melodies the press plays
 KEY_PARAMS = np.dtype([("freq", "<f4"), ("note_on", "<u4"), ("melody", "<u4")])
@@ -53,43 +54,19 @@ class MelodyKit:
             pass
 
 
-class SubsongTable:
-    """What a span paint takes (zh_script_span_table + zh_script_span_param): a view of the stage's table, no copy."""
-
-    def __init__(self, stage, max_spans):
-        self.stage, self.max_spans, self.n_voices = stage, max_spans, stage.n_players
-        self.tb = abi.ScriptSpanTable()
-        abi.check(stage.lib.zh_subsong_script_table(stage.handle, max_spans, C.byref(self.tb)), "zh_subsong_script_table")
-        self.arrays = {}
-        for name, field in (("freq", abi.SUBSONG_SPAN_FREQ), ("note_on", abi.SUBSONG_SPAN_NOTE_ON)):
-            sp = abi.ScriptSpanParam()
-            abi.check(stage.lib.zh_subsong_span_param(stage.handle, field, C.byref(sp)), "zh_subsong_span_param")
-            self.arrays[name] = sp
-
-    def device(self, dev, order):
-        sp = (abi.ScriptSpanParam * abi.SCRIPT_MAX_PARAMS)()
-        for i, name in enumerate(order):
-            if name in self.arrays:
-                sp[i] = self.arrays[name]
-        return self.tb, sp
+SubsongTable = StageTable
 
 
-class SubsongStage:
+class SubsongStage(Stage):
     """zh_subsong_*: n players' SubtrackPlayer.paint without the instrument.  `kit`: the MelodyKit they play from (it must outlive
     the stage); `base_freq`: the frequency the melodies are written at (:98).  schedule() reads the table of a LiveVoiceBank of
     polyphony 1 whose records are KEY_PARAMS and fills the stage's own table (script_table())."""
+    PREFIX = "zh_subsong"
+    FIELDS = (("freq", abi.SUBSONG_SPAN_FREQ), ("note_on", abi.SUBSONG_SPAN_NOTE_ON))
 
     def __init__(self, ctx, n_players, kit, base_freq=BASE_FREQ, rows=None):
-        self.ctx, self.lib, self.n_players, self.kit = ctx, ctx.lib, int(n_players), kit
-        self.handle = C.c_void_p()
-        abi.check(self.lib.zh_subsong_create(ctx.handle, self.n_players, kit.handle, float(base_freq), C.byref(self.handle)), "zh_subsong_create")
-        ctx._children.add(self)
-        if rows is not None:
-            self.reserve(rows)
-
-    def reserve(self, rows):
-        """table capacity in rows; invalidates views and graphs made before it"""
-        abi.check(self.lib.zh_subsong_reserve(self.handle, rows), "zh_subsong_reserve")
+        self.kit = kit
+        self._create(ctx, n_players, rows, kit.handle, float(base_freq))
 
     def reset(self):
         abi.check(self.lib.zh_subsong_reset(self.handle), "zh_subsong_reset")
@@ -102,15 +79,6 @@ class SubsongStage:
     def schedule(self, sample_rate, out_len, max_spans, outer):
         """one buffer: enqueued, no sync"""
         abi.check(self._schedule(sample_rate, out_len, max_spans, outer), "zh_subsong_schedule")
-
-    def script_table(self, max_spans):
-        return SubsongTable(self, max_spans)
-
-    def overflows(self):
-        """rows dropped so far because a player's list was full (synchronises)"""
-        n = C.c_uint64()
-        abi.check(self.lib.zh_subsong_overflows(self.handle, C.byref(n)), "zh_subsong_overflows")
-        return n.value
 
     def state(self):
         st = np.zeros(max(self.n_players, 1), np.dtype(abi.SubsongState))
@@ -125,28 +93,7 @@ class SubsongStage:
     def download(self, max_spans):
         """the stage's table as host arrays (synchronises; for tests and debugging): count [N], start / end / note_on [K][N]
         uint32, freq [K][N] float32, nic [K][N] uint8.  Rows at or above a player's count hold whatever was there."""
-        N, K = self.n_players, max_spans
-        t = self.script_table(K)
-
-        def down(ptr, shape, dtype):
-            a = np.zeros(shape, dtype)
-            if a.size:
-                abi.check(self.lib.zh_download(self.ctx.handle, a.ctypes.data, ptr, a.nbytes), "zh_download")
-            return a
-        return {"count": down(t.tb.count, (N,), np.uint32), "start": down(t.tb.start, (K, N), np.uint32), "end": down(t.tb.end, (K, N), np.uint32),
-                "nic": down(t.tb.note_id_changed, (K, N), np.uint8), "freq": down(t.arrays["freq"].f, (K, N), np.float32),
-                "note_on": down(t.arrays["note_on"].u, (K, N), np.uint32)}
-
-    def close(self):
-        if self.handle:
-            self.lib.zh_subsong_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:       # noqa: BLE001
-            pass
+        return super().download(max_spans, {"freq": np.float32})
 
 
 def key_table(bank, max_spans):

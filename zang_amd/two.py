@@ -9,6 +9,7 @@ import numpy as np
 
 from . import abi, modules as mod, zang
 from .bank import LiveVoiceBank
+from .stage import Stage, StageTable
 
 # the sources' records: Params0 / Params1 (:31-32), and a word that is always set for the bank's dispatcher (every push takes slot
 # 0, note-offs included: the bare Triggers of MainModule.paint)
@@ -19,26 +20,7 @@ MAX_SPANS = 67                                  # what two SOURCE_SPANS-row tabl
 A4 = 880.0                                      # :21
 
 
-class MergeTable:
-    """What a span paint takes (zh_script_span_table + zh_script_span_param): a view of the stage's table, no copy.  The arrays go
-    by the stage's field names."""
-
-    def __init__(self, stage, max_spans):
-        self.stage, self.max_spans, self.n_voices = stage, max_spans, stage.n_players
-        self.tb = abi.ScriptSpanTable()
-        abi.check(stage.lib.zh_span_merge_script_table(stage.handle, max_spans, C.byref(self.tb)), "zh_span_merge_script_table")
-        self.arrays = {}
-        for field, name in enumerate(stage.names):
-            sp = abi.ScriptSpanParam()
-            abi.check(stage.lib.zh_span_merge_span_param(stage.handle, field, C.byref(sp)), "zh_span_merge_span_param")
-            self.arrays[name] = sp
-
-    def device(self, dev, order):
-        sp = (abi.ScriptSpanParam * abi.SCRIPT_MAX_PARAMS)()
-        for i, name in enumerate(order):
-            if name in self.arrays:
-                sp[i] = self.arrays[name]
-        return self.tb, sp
+MergeTable = StageTable
 
 
 def _source(fields, on):
@@ -49,29 +31,23 @@ def _source(fields, on):
     return d
 
 
-class SpanMerge:
+class SpanMerge(Stage):
     """zh_span_merge_*: the loop of examples/example_two.zig:93-151 for n players, without the voice.  `fields_a` / `fields_b`: 1 to 4
     (name, "f" or "u") per source, the names those of the stage's output fields; `on_a` / `on_b`: the name of each source's note-on
     field (kind "u").  The output's fields: A's, then B's, then "note_on" (on_a | on_b), "nic_a" and "nic_b"; its note_id_changed
     is (nic_a & on_a & !nic_b) | (nic_b & on_b & !nic_a).  A source's nic stays set on every row cut from the same source row;
-    the sources' starts are never read; nothing follows once either source has no row left.  The stage keeps no state."""
+    the sources' starts are never read; nothing follows once either source has no row left.  The stage keeps no state.  The table
+    has 67 rows at creation; download() gives every field as uint32 words."""
+    PREFIX = "zh_span_merge"
 
     def __init__(self, ctx, n_players, fields_a, on_a, fields_b, on_b, rows=None):
-        self.ctx, self.lib, self.n_players = ctx, ctx.lib, int(n_players)
         self.fields_a, self.fields_b = list(fields_a), list(fields_b)
         self.names = [n for n, _ in self.fields_a] + [n for n, _ in self.fields_b] + ["note_on", "nic_a", "nic_b"]
         if len(set(self.names)) != len(self.names):
             raise ValueError("field names must differ (and from note_on, nic_a, nic_b)")
+        self.FIELDS = [(name, field) for field, name in enumerate(self.names)]
         a, b = _source(self.fields_a, on_a), _source(self.fields_b, on_b)
-        self.handle = C.c_void_p()
-        abi.check(self.lib.zh_span_merge_create(ctx.handle, self.n_players, C.byref(a), C.byref(b), C.byref(self.handle)), "zh_span_merge_create")
-        ctx._children.add(self)
-        if rows is not None:
-            self.reserve(rows)
-
-    def reserve(self, rows):
-        """table capacity in rows (67 at creation); invalidates views and graphs made before it"""
-        abi.check(self.lib.zh_span_merge_reserve(self.handle, rows), "zh_span_merge_reserve")
+        self._create(ctx, n_players, rows, C.byref(a), C.byref(b))
 
     def _schedule(self, out_len, max_spans, table_a, names_a, table_b, names_b):
         """-> the return code"""
@@ -83,44 +59,6 @@ class SpanMerge:
         """one buffer: enqueued, no sync.  `table_x`: a span table view (.tb, .arrays) such as a bank's script_table(); `names_x`:
         which of its arrays are the source's fields, in the order of fields_x"""
         abi.check(self._schedule(out_len, max_spans, table_a, names_a, table_b, names_b), "zh_span_merge_schedule")
-
-    def script_table(self, max_spans):
-        return MergeTable(self, max_spans)
-
-    def overflows(self):
-        """rows dropped so far because a player's list was full (synchronises)"""
-        n = C.c_uint64()
-        abi.check(self.lib.zh_span_merge_overflows(self.handle, C.byref(n)), "zh_span_merge_overflows")
-        return n.value
-
-    def download(self, max_spans):
-        """the stage's table as host arrays (synchronises; for tests and debugging): count [N], start / end [K][N] uint32, nic
-        [K][N] uint8, and every field by name, [K][N] uint32 (the words of an "f" field as bits).  Rows at or above a player's
-        count hold whatever was there."""
-        N, K = self.n_players, max_spans
-        t = self.script_table(K)
-
-        def down(ptr, shape, dtype):
-            a = np.zeros(shape, dtype)
-            if a.size:
-                abi.check(self.lib.zh_download(self.ctx.handle, a.ctypes.data, ptr, a.nbytes), "zh_download")
-            return a
-        out = {"count": down(t.tb.count, (N,), np.uint32), "start": down(t.tb.start, (K, N), np.uint32), "end": down(t.tb.end, (K, N), np.uint32),
-               "nic": down(t.tb.note_id_changed, (K, N), np.uint8)}
-        for name, sp in t.arrays.items():
-            out[name] = down(sp.f or sp.u, (K, N), np.uint32)
-        return out
-
-    def close(self):
-        if self.handle:
-            self.lib.zh_span_merge_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:       # noqa: BLE001
-            pass
 
 
 class TwoKeys:
