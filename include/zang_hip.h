@@ -1469,6 +1469,81 @@ ZH_API int zh_dual_paint_spans(zh_dual *m, uint32_t span_start, uint32_t span_en
                                const zh_script_span_param *span_params /*[ZH_DUAL_SPAN_FIELDS]*/,
                                const zh_script_span_table *table, uint32_t flags);                     /* the merge loop :101-151 */
 
+/* ---------------------------------------------------------------- the controlled phase-modulation voice as ONE fused kernel
+ * The PMOscInstrument of examples/example_mouse.zig:24-73 for n voices, one lane each: the PhaseModOscillator of
+ * examples/modules.zig:6-77 times an Envelope whose three curves are cubed.  Against zh_pmosc_* (modules.zig:80-128) `relative`
+ * is a parameter, ratio and multiplier are zang.ConstantOrBuffer SIGNALS and the release is a patch constant.  Per frame inside
+ * a note sub-span, with r = the ratio and m = the multiplier at the frame (every `0 +` is a zang.zero followed by a module's
+ * `+=`; no product is contracted with an add; s: "ONE DIFFERENCE" below):
+ *    mf   = relative ? s + r * freq : r       ratio a buffer, modules.zig:50-56 (multiplyScalar is `+=`; copy is a store)
+ *           relative ? freq * r     : r       ratio a constant, :43-49 (zang.set: s is not read)
+ *    mo   = 0 + sin((tm + 0.0) * 2 pi);  tm += mf * (1 / sample_rate)        the modulator, SineOsc's frequency-buffer path  :58-63
+ *    ph   = 0 + mo * m                                                       :64-68
+ *    c    = 0 + sin((tc + ph) * 2 pi);   tc += freq / sample_rate            the carrier, as zh_pmosc has it                 :69-74
+ *    o    = 0 + c                                                            :75 into the instrument's zeroed temps[0]
+ *    e    = 0 + env        (a frame the Envelope does not paint keeps the 0)                          example_mouse.zig:62-70
+ *    out += o * e                                                            :71 (the product is rounded, then added)
+ * Both oscillators' epilogues (t -= trunc(t)) run at the end of every sub-span, both prologues and the Envelope's at the start of
+ * each; note_id_changed goes to all three modules.  Frames outside every note sub-span touch neither the output nor the voice's
+ * state.
+ * ONE DIFFERENCE, made explicit: the reference's oscillator adds `r * freq` into ITS temps[0] without zeroing it first
+ * (modules.zig:52), and that row is the instrument's temps[1], into which the instrument later paints the Envelope
+ * (example_mouse.zig:62-63): s at frame i is the envelope value of the last paint that covered buffer index i.  Here the paints
+ * take temps[3]: if temps is not NULL and temps[1].ptr is not NULL, that [frame][voice] image is read as s before the frame (in
+ * the relative / buffer branch only) and e is stored into it after the frame (in every branch); the caller keeps the image between
+ * calls, and that is the reference bit for bit.  If it is NULL, s = +0.0 and nothing is stored.  temps[0] and temps[2] are never
+ * touched.
+ * zh_pmctl_paint is `paint` of :46-72: a constant ratio / multiplier may be per-voice, a buffer is a [frame][voice] image indexed
+ * by ABSOLUTE frame.  zh_pmctl_paint_spans is the Trigger loop of :193-211 over a table of notes with the contract of
+ * zh_porta_paint_spans.  zh_pmctl_paint_controlled is the whole of MainModule.paint (:148-211) in one kernel: each control is the
+ * Trigger loop of :151-169 / :175-190 around a Portamento -- at each of ITS sub-spans porta.begin(sample_rate, patch.ctl_curve,
+ * patch.ctl_glide, goal = value * scale, note_on, prev_note_on = true, that sub-span's note_id_changed); at a frame inside one of
+ * its sub-spans the control's value is 0 + the Portamento's frame, outside all of them +0.0 (:149, :172) and its state does not
+ * move.  The three streams' boundaries are unrelated; each table follows the contract of zh_detuned_paint_spans on its own (an
+ * empty sub-span runs its prologue and epilogue; a sub-span out of order ends THAT stream's list while the other two go on);
+ * the controls advance over all of [span_start, span_end) whether or not a note sounds.  In this form the ratio and the
+ * multiplier are buffers (the relative / buffer branch reads s).
+ * The three paints allocate nothing and never synchronise: capturable.  ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end)
+ * of outputs[0]; ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED.  ZH_ERR_INVALID: what zh_dual_paint[_spans] refuses, a zh_cob with an
+ * unknown tag, a cob buffer or a temps[1] that is too small, a control that is NULL or has a NULL table, table array, value.f or
+ * note_on.u, a value with `u` or a note_on with `f`. */
+typedef struct zh_pmctl zh_pmctl;
+typedef struct zh_pmctl_patch {            /* the reference's constants; uniform over a call */
+    uint32_t ctl_curve; float ctl_glide;   /* ZH_CURVE_LINEAR, 0.1        example_mouse.zig:160, :184 */
+    float attack, decay, release, sustain_volume;   /* cubed 0.025, 0.1, 1.0; 0.5   :65-68 */
+} zh_pmctl_patch;
+typedef struct zh_pmctl_params {
+    float sample_rate; uint32_t reserved;
+    zh_f32 freq; zh_bool note_on; zh_bool relative;   /* broadcast or per-voice device arrays */
+    zh_pmctl_patch patch;
+} zh_pmctl_params;
+typedef struct zh_pmctl_state { zh_portamento_state ratio, multiplier; zh_sineosc_state carrier, modulator; zh_envelope_state env; } zh_pmctl_state;
+enum { ZH_PMCTL_SPAN_FREQ = 0 /* f */, ZH_PMCTL_SPAN_NOTE_ON /* u */, ZH_PMCTL_SPAN_FIELDS };
+typedef struct zh_pmctl_control {
+    const zh_script_span_table *table;     /* the control's own sub-spans, e.g. of a live bank of polyphony 1 */
+    zh_script_span_param value;            /* f: result.params.value */
+    zh_script_span_param note_on;          /* u: result.params.note_on */
+    zh_f32 scale;                          /* goal = value * scale: 4.0 or 880.0 (:161-164), 2.0 (:185); one f32 multiply */
+} zh_pmctl_control;
+ZH_API int zh_pmctl_patch_default(zh_pmctl_patch *patch);
+ZH_API int zh_pmctl_create(zh_ctx *ctx, uint32_t n_voices, zh_pmctl **out);                            /* init(): every word zero */
+ZH_API int zh_pmctl_destroy(zh_pmctl *m);
+ZH_API int zh_pmctl_get_state(zh_pmctl *m, zh_pmctl_state *host);
+ZH_API int zh_pmctl_set_state(zh_pmctl *m, const zh_pmctl_state *host);
+ZH_API int zh_pmctl_paint(zh_pmctl *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[1]*/,
+                          const zh_buf *temps /*[3]; NULL or temps[1].ptr NULL: no carried image*/, zh_bool note_id_changed,
+                          const zh_pmctl_params *params, const zh_cob *ratio, const zh_cob *multiplier, uint32_t flags);   /* :46-72 */
+ZH_API int zh_pmctl_paint_spans(zh_pmctl *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[1]*/,
+                                const zh_buf *temps /*[3]*/, const zh_pmctl_params *params,
+                                const zh_script_span_param *span_params /*[ZH_PMCTL_SPAN_FIELDS]*/,
+                                const zh_script_span_table *table, const zh_cob *ratio, const zh_cob *multiplier,
+                                uint32_t flags);                                                       /* the Trigger loop :193-211 */
+ZH_API int zh_pmctl_paint_controlled(zh_pmctl *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[1]*/,
+                                     const zh_buf *temps /*[3]*/, const zh_pmctl_params *params,
+                                     const zh_script_span_param *span_params /*[ZH_PMCTL_SPAN_FIELDS]*/,
+                                     const zh_script_span_table *notes_table, const zh_pmctl_control *ratio_ctl,
+                                     const zh_pmctl_control *multiplier_ctl, uint32_t flags);          /* MainModule.paint :148-211 */
+
 /* The zangscript compiler itself (host side, no GPU work): src/zangscript/{tokenize,parse,codegen}.zig restated in
  * C++ (csrc/zscript_front.hip) with both backends (csrc/zscript_emit.hip): the reference's Zig text
  * (codegen_zig.zig; pins the front-end against the golden of src/zangscript/tests.zig:44-92) and the HIP source

@@ -673,6 +673,45 @@ public:
     }
 };
 
+// The PMOscInstrument of examples/example_mouse.zig (:24-73) for n voices as one fused kernel: `relative` is a parameter, ratio and
+// multiplier are zh_cob signals.  temps: nullptr, or three zh_buf of which [1] may be the carried image of the reference's stale temp
+// (zang_hip.h, "ONE DIFFERENCE").  paintControlled is MainModule.paint (:148-211): each control a Portamento over its own table.
+class PMCtl {
+    zh_pmctl *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 1;
+    static constexpr size_t num_temps = 3;
+    using Params = zh_pmctl_params;
+    using Patch = zh_pmctl_patch;
+    using State = zh_pmctl_state;
+    using Control = zh_pmctl_control;
+    PMCtl(Context &ctx, uint32_t n_voices) { check(zh_pmctl_create(ctx.get(), n_voices, &h_), "zh_pmctl_create"); }
+    ~PMCtl() { if (h_) zh_pmctl_destroy(h_); }
+    PMCtl(const PMCtl &) = delete;
+    PMCtl &operator=(const PMCtl &) = delete;
+    zh_pmctl *get() const { return h_; }
+    static Patch defaultPatch() { Patch p{}; check(zh_pmctl_patch_default(&p), "zh_pmctl_patch_default"); return p; }
+    void getState(State *host) const { check(zh_pmctl_get_state(h_, host), "zh_pmctl_get_state"); }
+    void setState(const State *host) { check(zh_pmctl_set_state(h_, host), "zh_pmctl_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 1> &outputs, const zh_buf *temps, zh_bool note_id_changed, const Params &params,
+               const zh_cob &ratio, const zh_cob &multiplier, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_pmctl_paint(h_, span.start, span.end, outputs.data(), temps, note_id_changed, &params, &ratio, &multiplier, flags), "zh_pmctl_paint");
+    }
+    // the Trigger loop (:193-211) for every voice in one call; span_params = host array [ZH_PMCTL_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 1> &outputs, const zh_buf *temps, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, const zh_cob &ratio, const zh_cob &multiplier, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_pmctl_paint_spans(h_, span.start, span.end, outputs.data(), temps, &params, span_params, &table, &ratio, &multiplier, flags),
+              "zh_pmctl_paint_spans");
+    }
+    void paintControlled(Span span, const std::array<zh_buf, 1> &outputs, const zh_buf *temps, const Params &params,
+                         const zh_script_span_param *span_params, const zh_script_span_table &notes, const Control &ratio, const Control &multiplier,
+                         uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_pmctl_paint_controlled(h_, span.start, span.end, outputs.data(), temps, &params, span_params, &notes, &ratio, &multiplier, flags),
+              "zh_pmctl_paint_controlled");
+    }
+};
+
 }  // namespace zang
 
 namespace mod {

@@ -25,7 +25,7 @@ OUT = os.path.join(ROOT, "bindings", "zang_hip.zig")
 
 SCALARS = {"int": "c_int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "uint8_t": "u8", "float": "f32", "double": "f64",
            "size_t": "usize", "char": "u8", "long": "c_long"}
-WORDS = {"sineosc": "SineOsc", "pulseosc": "PulseOsc", "trisawosc": "TriSawOsc", "pmosc": "PMOsc", "f32": "F32", "cob": "Cob",
+WORDS = {"sineosc": "SineOsc", "pulseosc": "PulseOsc", "trisawosc": "TriSawOsc", "pmosc": "PMOsc", "pmctl": "PMCtl", "f32": "F32", "cob": "Cob",
          "hcob": "HCob", "hcurve": "HCurve", "iap": "Iap", "zscript": "ZScript", "ipc": "Ipc"}
 
 # (module key, Zig wrapper name, num_temps of the reference module, reference file, extra create args)
@@ -74,6 +74,7 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 # n_fields entries per source
                 ("zh_span_merge_schedule", "fields_a"), ("zh_span_merge_schedule", "fields_b"),
                 ("zh_dual_paint_spans", "span_params"),
+                ("zh_pmctl_paint_spans", "span_params"), ("zh_pmctl_paint_controlled", "span_params"),
                 # n effects; the nine nodes of the default effect
                 ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
                 # n samples

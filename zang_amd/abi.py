@@ -391,6 +391,26 @@ class DualState(C.Structure):              # zh_dual_state: the field order of e
 DUAL_SPAN_FREQ, DUAL_SPAN_COLOR, DUAL_SPAN_NOTE_ON, DUAL_SPAN_FIELDS = range(4)
 
 
+class PMCtlPatch(C.Structure):             # zh_pmctl_patch: the constants of examples/example_mouse.zig:160, :184, :65-68
+    _fields_ = [("ctl_curve", u32), ("ctl_glide", f32), ("attack", f32), ("decay", f32), ("release", f32), ("sustain_volume", f32)]
+
+
+class PMCtlParams(C.Structure):            # zh_pmctl_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("freq", F32), ("note_on", Bool), ("relative", Bool), ("patch", PMCtlPatch)]
+
+
+class PMCtlState(C.Structure):             # zh_pmctl_state: the two controls' Portamentos, then PMOscInstrument's modules
+    _fields_ = [("ratio", PortamentoState), ("multiplier", PortamentoState), ("carrier", SineOscState), ("modulator", SineOscState),
+                ("env", EnvelopeState)]
+
+
+class PMCtlControl(C.Structure):           # zh_pmctl_control: one control stream of zh_pmctl_paint_controlled
+    _fields_ = [("table", C.POINTER(ScriptSpanTable)), ("value", ScriptSpanParam), ("note_on", ScriptSpanParam), ("scale", F32)]
+
+
+PMCTL_SPAN_FREQ, PMCTL_SPAN_NOTE_ON, PMCTL_SPAN_FIELDS = range(3)
+
+
 class SpanTable(C.Structure):
     _fields_ = [("max_spans", u32), ("reserved", u32), ("count", vp), ("start", vp), ("end", vp), ("freq", vp),
                 ("note_on", vp), ("note_id_changed", vp)]
@@ -766,6 +786,14 @@ SIGNATURES = {
     "zh_dual_set_state": (C.c_int, [vp, vp]),
     "zh_dual_paint": (C.c_int, _paint(DualParams)),
     "zh_dual_paint_spans": (C.c_int, _paint_spans(DualParams)),
+    "zh_pmctl_patch_default": (C.c_int, [P(PMCtlPatch)]),
+    "zh_pmctl_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_pmctl_destroy": (C.c_int, [vp]),
+    "zh_pmctl_get_state": (C.c_int, [vp, vp]),
+    "zh_pmctl_set_state": (C.c_int, [vp, vp]),
+    "zh_pmctl_paint": (C.c_int, _paint(PMCtlParams)[:-1] + [P(Cob), P(Cob), u32]),
+    "zh_pmctl_paint_spans": (C.c_int, _paint_spans(PMCtlParams)[:-1] + [P(Cob), P(Cob), u32]),
+    "zh_pmctl_paint_controlled": (C.c_int, _paint_spans(PMCtlParams)[:-1] + [P(PMCtlControl), P(PMCtlControl), u32]),
     "zh_melody_kit_create": (C.c_int, [vp, vp, u32, vp, u32, P(vp)]),
     "zh_melody_kit_destroy": (C.c_int, [vp]),
     "zh_melody_kit_count": (C.c_int, [vp, P(u32), P(u32)]),

@@ -1059,3 +1059,116 @@ class Dual(_Lead):
         p = params.patch or Dual.Patch()
         patch = abi.DualPatch(p.attack, p.decay, p.release, p.sustain_volume)
         return abi.DualParams(params.sample_rate, 0, as_f32(params.freq), as_f32(params.color), as_bool(params.note_on), patch)
+
+
+class PMCtl(_Module):
+    """examples/example_mouse.zig:24-73 over examples/modules.zig:6-77: the phase-modulation instrument whose `relative` is a
+    parameter and whose ratio and multiplier are signals, as one fused kernel.  paint() and paint_spans() take the two as
+    zang.constant(...) (a float, or per voice) or zang.buffer(image); paint_controlled() is MainModule.paint (:148-211): each of
+    the two is a Portamento driven by its own sub-span table (a Control), painted in registers under the voice.  `temps`: None, or
+    three entries of which [1] may be a [frame][voice] image the caller keeps between calls -- the reference's stale temp
+    (include/zang_hip.h, "ONE DIFFERENCE"): read in the relative / buffer branch, overwritten with the envelope's temp."""
+    _prefix = "pmctl"
+    _state_ctype = abi.PMCtlState
+    num_temps = 3
+    _span_fields = (("freq", "constant"), ("note_on", "boolean"))
+    _control_fields = (("value", "constant"), ("note_on", "boolean"))
+
+    @dataclass
+    class Patch:                    # the reference's constants (:160, :184, :65-68)
+        ctl_curve: int = abi.CURVE_LINEAR
+        ctl_glide: float = 0.1
+        attack: float = 0.025       # the three curves are cubed
+        decay: float = 0.1
+        release: float = 1.0
+        sustain_volume: float = 0.5
+
+    @dataclass
+    class Params:
+        sample_rate: float
+        freq: Any = 220.0           # float, or float32 CUDA tensor [n_voices]
+        note_on: Any = True         # bool, or uint8 / bool CUDA tensor [n_voices]
+        relative: Any = True        # bool, or uint8 / bool CUDA tensor [n_voices]
+        patch: Any = None           # PMCtl.Patch; None = the reference's
+
+    @dataclass
+    class Control:
+        """one control stream: `table` a span table view with arrays named `value` (f) and `note_on` (u), e.g. a live bank's
+        script_table() or control_table(); goal = value * scale (a float, or float32 CUDA tensor [n_voices])"""
+        table: Any
+        scale: Any = 1.0
+        value: str = "value"
+        note_on: str = "note_on"
+
+    @staticmethod
+    def _cparams(params):
+        p = params.patch or PMCtl.Patch()
+        patch = abi.PMCtlPatch(int(p.ctl_curve), p.ctl_glide, p.attack, p.decay, p.release, p.sustain_volume)
+        return abi.PMCtlParams(params.sample_rate, 0, as_f32(params.freq), as_bool(params.note_on), as_bool(params.relative), patch)
+
+    @classmethod
+    def control_table(cls, count, start, end, note_id_changed, value, note_on):
+        """a control's sub-span table from host arrays: count [V]; the rest [K][V]"""
+        from .script import ScriptSpanTable
+        return ScriptSpanTable([(n, k, None) for n, k in cls._control_fields], count, start, end, note_id_changed,
+                               {"value": (value, None), "note_on": (None, note_on)})
+
+    @staticmethod
+    def _temps(temps):
+        if not temps or len(temps) < 2 or temps[1] is None:
+            return None
+        arr = (abi.Buf * 3)()
+        arr[1] = as_buf(temps[1])
+        return arr
+
+    def _control(self, ctl):
+        tb, sp = ctl.table.device(self.ctx.device, [ctl.value, ctl.note_on])
+        c = abi.PMCtlControl(C.pointer(tb), sp[0], sp[1], as_f32(ctl.scale))
+        c._keep = (tb, sp, ctl)
+        return c
+
+    def _paint_rc(self, span, outputs, temps, note_id_changed, params, ratio, multiplier, flags):
+        cp = self._cparams(params)
+        rc = self.lib.zh_pmctl_paint(self.handle, span.start, span.end, _bufarray(outputs), self._temps(temps), as_bool(note_id_changed),
+                                     C.byref(cp), C.byref(ratio), C.byref(multiplier), flags)
+        self._keep = (cp, outputs, temps, ratio, multiplier)
+        return rc
+
+    def paint(self, span, outputs, temps, note_id_changed, params, ratio, multiplier, zero_first=False):
+        abi.check(self._paint_rc(span, outputs, temps, note_id_changed, params, ratio, multiplier,
+                                 abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD), "zh_pmctl_paint")
+
+    def _paint_spans(self, span, outputs, temps, params, table, flags, span_params=None, ratio=None, multiplier=None):
+        from . import zang
+        cp = self._cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._span_fields])
+        if span_params is not None:
+            sp = span_params
+        ratio = zang.constant(1.0) if ratio is None else ratio
+        multiplier = zang.constant(1.0) if multiplier is None else multiplier
+        rc = self.lib.zh_pmctl_paint_spans(self.handle, span.start, span.end, _bufarray(outputs), self._temps(temps), C.byref(cp), sp, C.byref(tb),
+                                           C.byref(ratio), C.byref(multiplier), flags)
+        self._keep = (cp, outputs, temps, table, ratio, multiplier)
+        return rc
+
+    def paint_spans(self, span, outputs, temps, params, table, ratio=None, multiplier=None, zero_first=False):
+        """the Trigger loop of :193-211 for every voice in one launch; ratio / multiplier: cobs, None = constant 1.0"""
+        rc = self._paint_spans(span, outputs, temps, params, table, abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD, None, ratio, multiplier)
+        abi.check(rc, "zh_pmctl_paint_spans")
+
+    def _paint_controlled(self, span, outputs, temps, params, table, ratio_ctl, multiplier_ctl, flags, span_params=None):
+        cp = self._cparams(params)
+        tb, sp = table.device(self.ctx.device, [n for n, _ in self._span_fields])
+        if span_params is not None:
+            sp = span_params
+        rc_, mc_ = self._control(ratio_ctl), self._control(multiplier_ctl)
+        rc = self.lib.zh_pmctl_paint_controlled(self.handle, span.start, span.end, _bufarray(outputs), self._temps(temps), C.byref(cp), sp,
+                                                C.byref(tb), C.byref(rc_), C.byref(mc_), flags)
+        self._keep = (cp, outputs, temps, table, rc_, mc_)
+        return rc
+
+    def paint_controlled(self, span, outputs, temps, params, table, ratio_ctl, multiplier_ctl, zero_first=False):
+        """MainModule.paint (:148-211) for every voice in ONE launch: `table` the notes' sub-spans, the two Controls' their own"""
+        rc = self._paint_controlled(span, outputs, temps, params, table, ratio_ctl, multiplier_ctl,
+                                    abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD)
+        abi.check(rc, "zh_pmctl_paint_controlled")
