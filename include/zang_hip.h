@@ -1112,6 +1112,57 @@ ZH_API int zh_detuned_paint_spans(zh_detuned *m, uint32_t span_start, uint32_t s
                                   const zh_detuned_params *params, const zh_script_span_param *span_params /*[ZH_DETUNED_SPAN_FIELDS]*/,
                                   const zh_script_span_table *table, uint32_t flags);                  /* the Trigger loop :213-222 */
 
+/* ---------------------------------------------------------------- curve voice (examples/example_curve.zig:18-96)
+ * CurvePlayer as ONE kernel: two Curves (modulator frequency, carrier frequency) drive a phase-modulated pair of SineOscs.  There
+ * is no volume curve: the carrier adds straight into outputs[0], and its frequency image is added into outputs[1] (the reference's
+ * oscilloscope sync).  Bit-identical to the reference's stage order; per frame i of a sub-span [s, e), r = i - s (Cm, Cc = the
+ * effect's modulator and carrier curves; Zig lines on the right):
+ *   f_m    = (0 + Cm(r)) * rel_freq                     (a frame the curve does not paint is +0.0)                 :65-71
+ *   p      = 0 + sin((t_m + 0) * pi * 2);  t_m += f_m * (1 / sample_rate)                                          :73-78
+ *   f_c    = (0 + Cc(r)) * rel_freq                                                                                :80-86
+ *   out0  += sin((t_c + p) * pi * 2);      t_c += f_c * (1 / sample_rate)      (no `0 +`: added into the output itself)   :88-92
+ *   out1  += f_c                           (on EVERY frame of the sub-span, a +-0.0 or NaN addend too; skipped when outputs[1].ptr is NULL)   :94
+ * and after the sub-span t_m -= trunc(t_m), t_c -= trunc(t_c).  Every `0 +` is zang.zero followed by a module's `+=` (-0.0 becomes
+ * +0.0); where the reference zeroes no temp there is none: a sine of -0.0 added to a -0.0 in outputs[0] stays -0.0.
+ * The curves come from an effect kit (zh_sfx_kit, above, unchanged): the voice plays effect e's `modulator` and `carrier` and never
+ * reads `volume`, which may have count 0.  zh_sfx_effect_curve_example fills in the reference's pair (nodes[0..2] = the modulator
+ * of :27-31, nodes[3..8] = the carrier of :18-25, both smoothstep, volume {NULL, 0, smoothstep}).  All of zh_laser's kit semantics
+ * carry over: each of the two curves behaves exactly as zh_curve_module_paint does and reads its carried node at the index the
+ * previous paint left, counted from the first node of the curve it plays NOW (the kit's zero tail keeps that read inside the
+ * array; an index past the array, which only zh_curve_player_set_state can produce, drops the carried node).  An effect index >=
+ * the kit's count is DEFINED: nothing is painted, none of the ten state words changes, no node is read and neither output is
+ * touched -- even when note_id_changed is set.  A sound outlives buffers (the example's curves run 3.9 s): the state carries it.
+ * zh_curve_player_paint_spans is the Trigger loop of :126-129 for every voice in one launch, with the contract of
+ * zh_detuned_paint_spans: empty sub-spans run their prologue, a sub-span out of order ends the voice's list, ZH_PAINT_ZERO_FIRST
+ * writes all of [span_start, span_end) of BOTH painted outputs (a zero followed by an add paint), ZH_PAINT_TOLERANT is
+ * ZH_ERR_UNSUPPORTED; frames outside every sub-span touch nothing; a field without a span array takes its value from `params` (a
+ * broadcast value or a per-voice device array).  zh_curve_player_paint is the same kernel over one sub-span per voice.  Neither
+ * paint allocates or synchronises: both are capturable, and paints, span paints and graph replays of one zh_curve_player mix.
+ * ZH_ERR_INVALID: what zh_laser_paint[_spans] refuses, an outputs[1] that is not NULL and too small. */
+typedef struct zh_curve_player zh_curve_player;
+typedef struct zh_curve_player_params {                                                                /* :36-39 */
+    float sample_rate; uint32_t reserved;
+    zh_f32 rel_freq;
+    zh_u32 effect;         /* index into the kit */
+    const zh_sfx_kit *kit;
+} zh_curve_player_params;
+typedef struct zh_curve_player_state {                                                                 /* :41-44 */
+    zh_curve_module_state carrier_curve; zh_sineosc_state carrier;
+    zh_curve_module_state modulator_curve; zh_sineosc_state modulator;
+} zh_curve_player_state;
+enum { ZH_CURVE_PLAYER_SPAN_REL_FREQ = 0 /* f */, ZH_CURVE_PLAYER_SPAN_EFFECT /* u */, ZH_CURVE_PLAYER_SPAN_FIELDS };
+ZH_API int zh_sfx_effect_curve_example(zh_sfx_effect *effect, zh_curve_node *nodes /*[9]: what the effect's curves point at*/);
+ZH_API int zh_curve_player_create(zh_ctx *ctx, uint32_t n_voices, zh_curve_player **out);              /* init() :46-53 */
+ZH_API int zh_curve_player_destroy(zh_curve_player *m);
+ZH_API int zh_curve_player_get_state(zh_curve_player *m, zh_curve_player_state *host);
+ZH_API int zh_curve_player_set_state(zh_curve_player *m, const zh_curve_player_state *host);
+ZH_API int zh_curve_player_paint(zh_curve_player *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/,
+                                 const zh_buf *temps /*[2], unused; may be NULL*/,
+                                 zh_bool note_id_changed, const zh_curve_player_params *params, uint32_t flags);   /* :55-95 */
+ZH_API int zh_curve_player_paint_spans(zh_curve_player *m, uint32_t span_start, uint32_t span_end, const zh_buf *outputs /*[2]*/, const zh_buf *temps,
+                                       const zh_curve_player_params *params, const zh_script_span_param *span_params /*[ZH_CURVE_PLAYER_SPAN_FIELDS]*/,
+                                       const zh_script_span_table *table, uint32_t flags);             /* the Trigger loop :126-129 */
+
 /* ---------------------------------------------------------------- the monophonic leads: glide and vibrato voices
  * The two lead instruments of the reference's examples, each as ONE kernel.  They share one Params record (sample_rate, freq,
  * note_on) and both paint two outputs: outputs[0] = the voice, outputs[1] = the frequency image (the reference's oscilloscope

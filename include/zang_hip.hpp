@@ -429,6 +429,34 @@ public:
     }
 };
 
+// CurvePlayer (examples/example_curve.zig:33-96) for n voices as one fused kernel: outputs[0] = the voice, outputs[1] = the carrier's
+// frequency image (a zh_buf{} whose ptr is NULL: not painted); the modulator and carrier curves come from an SfxKit
+class CurvePlayer {
+    zh_curve_player *h_ = nullptr;
+
+public:
+    static constexpr size_t num_outputs = 2;
+    static constexpr size_t num_temps = 2;
+    using Params = zh_curve_player_params;
+    using State = zh_curve_player_state;
+    CurvePlayer(Context &ctx, uint32_t n_voices) { check(zh_curve_player_create(ctx.get(), n_voices, &h_), "zh_curve_player_create"); }
+    ~CurvePlayer() { if (h_) zh_curve_player_destroy(h_); }
+    CurvePlayer(const CurvePlayer &) = delete;
+    CurvePlayer &operator=(const CurvePlayer &) = delete;
+    zh_curve_player *get() const { return h_; }
+    void getState(State *host) const { check(zh_curve_player_get_state(h_, host), "zh_curve_player_get_state"); }
+    void setState(const State *host) { check(zh_curve_player_set_state(h_, host), "zh_curve_player_set_state"); }
+    void paint(Span span, const std::array<zh_buf, 2> &outputs, zh_bool note_id_changed, const Params &params, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_curve_player_paint(h_, span.start, span.end, outputs.data(), nullptr, note_id_changed, &params, flags), "zh_curve_player_paint");
+    }
+    // MainModule's Trigger loop (:126-129) for every voice in one call; span_params = host array [ZH_CURVE_PLAYER_SPAN_FIELDS] or nullptr
+    void paintSpans(Span span, const std::array<zh_buf, 2> &outputs, const Params &params, const zh_script_span_param *span_params,
+                    const zh_script_span_table &table, uint32_t flags = ZH_PAINT_ADD) {
+        check(zh_curve_player_paint_spans(h_, span.start, span.end, outputs.data(), nullptr, &params, span_params, &table, flags),
+              "zh_curve_player_paint_spans");
+    }
+};
+
 // Instrument of examples/example_portamento.zig (:20-87) for n voices as one fused kernel: a sine whose frequency glides toward
 // the note's, times an envelope; the voice carries prev_note_on across sub-spans.  outputs[0] = the voice, outputs[1] = the
 // frequency image (a zh_buf{} whose ptr is NULL: not painted)

@@ -77,6 +77,7 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 ("zh_pmctl_paint_spans", "span_params"), ("zh_pmctl_paint_controlled", "span_params"),
                 # n effects; the nine nodes of the default effect
                 ("zh_sfx_kit_create", "effects"), ("zh_sfx_effect_default", "nodes"),
+                ("zh_sfx_effect_curve_example", "nodes"), ("zh_curve_player_paint_spans", "span_params"),
                 # n samples
                 ("zh_sample_kit_create", "samples"),
                 # the batch call reads n_buffers elements of each

@@ -273,6 +273,18 @@ class LaserState(C.Structure):             # zh_laser_state: the field order of 
 LASER_SPAN_FREQ_MUL, LASER_SPAN_CARRIER_MUL, LASER_SPAN_MODULATOR_MUL, LASER_SPAN_MODULATOR_RAD, LASER_SPAN_EFFECT, LASER_SPAN_FIELDS = range(6)
 
 
+class CurvePlayerParams(C.Structure):      # zh_curve_player_params
+    _fields_ = [("sample_rate", f32), ("reserved", u32), ("rel_freq", F32), ("effect", U32), ("kit", vp)]
+
+
+class CurvePlayerState(C.Structure):       # zh_curve_player_state: the field order of examples/example_curve.zig:41-44
+    _fields_ = [("carrier_curve", CurveModuleState), ("carrier", SineOscState), ("modulator_curve", CurveModuleState),
+                ("modulator", SineOscState)]
+
+
+CURVE_PLAYER_SPAN_REL_FREQ, CURVE_PLAYER_SPAN_EFFECT, CURVE_PLAYER_SPAN_FIELDS = range(3)
+
+
 class DetunedPatch(C.Structure):           # zh_detuned_patch: the constants of examples/example_detuned.zig
     _fields_ = [("warble_hz", f32), ("warble_wide", f32), ("color", f32), ("volume", f32), ("attack", f32), ("decay", f32),
                 ("release", f32), ("sustain_volume", f32), ("cutoff_hz", f32), ("res", f32)]
@@ -728,6 +740,13 @@ SIGNATURES = {
     "zh_laser_set_state": (C.c_int, [vp, vp]),
     "zh_laser_paint": (C.c_int, _paint(LaserParams)),
     "zh_laser_paint_spans": (C.c_int, _paint_spans(LaserParams)),
+    "zh_sfx_effect_curve_example": (C.c_int, [P(SfxEffect), P(CurveNode)]),
+    "zh_curve_player_create": (C.c_int, [vp, u32, P(vp)]),
+    "zh_curve_player_destroy": (C.c_int, [vp]),
+    "zh_curve_player_get_state": (C.c_int, [vp, vp]),
+    "zh_curve_player_set_state": (C.c_int, [vp, vp]),
+    "zh_curve_player_paint": (C.c_int, _paint(CurvePlayerParams)),
+    "zh_curve_player_paint_spans": (C.c_int, _paint_spans(CurvePlayerParams)),
     "zh_detuned_patch_default": (C.c_int, [P(DetunedPatch)]),
     "zh_detuned_create": (C.c_int, [vp, u32, u64, P(vp)]),
     "zh_detuned_destroy": (C.c_int, [vp]),

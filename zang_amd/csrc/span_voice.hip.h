@@ -1,5 +1,5 @@
 // span_voice.hip.h -- what the fused voices that paint one LANE per voice from a span table share (lead.hip, hard_square.hip,
-// saw_env.hip, detuned.hip; laser.hip takes the host side alone).  Three parts:
+// saw_env.hip, detuned.hip; laser.hip takes the host side alone, curve_player.hip all but the kernel's body).  Three parts:
 //   the float <-> word pair of every state layout, as plain C++ (the stand-alone harnesses of tests/cpp include it);
 //   the device side (hipcc only): the frame loop over one or two columns, and ZH_SPAN_VOICE_KERNEL, the kernel on span_walk's
 //   segments under each voice's stable kernel name;
@@ -15,7 +15,7 @@
 inline uint32_t zh_f32_bits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
 inline float zh_bits_f32(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
 
-// A Layout (PortaLayout, VibratoLayout, HardSquareLayout, SawEnvLayout, DetunedLayout, LaserLayout) is what the host side reads of
+// A Layout (PortaLayout, VibratoLayout, HardSquareLayout, SawEnvLayout, DetunedLayout, LaserLayout, CurvePlayerLayout) is what the host side reads of
 // a voice's state, plain C++ beside the voice's struct:
 //   State                                   the ABI struct of one voice
 //   kWords                                  words per voice; the device block is uint32_t[kWords][n]
@@ -105,7 +105,7 @@ __device__ __forceinline__ void span_voice_frames(L &n, const Img &out, const Im
     };
 
 // ---- the host side -----------------------------------------------------------------------------------------------------
-// the base of the voices' opaque handles (zh_porta, zh_vibrato, zh_hard_square, zh_saw_env, zh_detuned, zh_laser)
+// the base of the voices' opaque handles (zh_porta, zh_vibrato, zh_hard_square, zh_saw_env, zh_detuned, zh_laser, zh_curve_player)
 struct zh_voice {
     zh_ctx *ctx;
     uint32_t n;

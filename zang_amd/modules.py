@@ -919,6 +919,30 @@ class _Lead(_Module):
         return rc
 
 
+class CurveVoice(_Lead):
+    """examples/example_curve.zig:33-96: CurvePlayer -- two Curves (modulator frequency, carrier frequency) driving a
+    phase-modulated pair of SineOscs, the carrier added straight into the output -- as one fused kernel.  outputs = [voice image]
+    or [voice image, frequency image] (the reference's oscilloscope sync; None or left out: not painted).  The curves come from
+    an effect kit (zang_amd.sfx.SfxKit; sfx.curve_example_effect() is the reference's pair): the voice plays an effect's
+    modulator and carrier curves and never reads its volume curve."""
+    _prefix = "curve_player"
+    _state_ctype = abi.CurvePlayerState
+    num_temps = 2
+
+    @dataclass
+    class Params:
+        kit: Any                    # SfxKit
+        sample_rate: float
+        rel_freq: Any = 1.0         # float, or float32 CUDA tensor [n_voices]
+        effect: Any = 0             # int, or int32 CUDA tensor [n_voices]: the index into the kit
+
+    _span_fields = (("rel_freq", "constant"), ("effect", "tag"))
+
+    @staticmethod
+    def _cparams(params):
+        return abi.CurvePlayerParams(params.sample_rate, 0, as_f32(params.rel_freq), as_u32(params.effect), params.kit.handle)
+
+
 class Porta(_Lead):
     """examples/example_portamento.zig:20-87: a sine whose frequency glides toward the note's (Portamento), scaled by an Envelope,
     as one fused kernel.  The voice carries prev_note_on across sub-spans and buffers: the glide is instantaneous and the

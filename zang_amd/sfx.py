@@ -3,7 +3,8 @@ laser examples (examples/example_laser.zig MainModule, :119-223) played live.  T
 (:22-38) and gets its four sounds from four scalars (:161-220); here a pushed impulse also names an effect of the kit.  Per
 buffer: the pushed impulses go through one LiveVoiceBank launch (ImpulseQueue -> PolyphonyDispatcher -> Triggers) and one
 zh_laser_paint_spans renders every voice's sub-spans with each impulse's effect and scalars (:149-158); with more than one
-voice per player the grouped mixdown adds each player's voices in voice order."""
+voice per player the grouped mixdown adds each player's voices in voice order.  CurvePlayer does the same for the curve voice of
+examples/example_curve.zig (zh_curve_player_paint_spans), whose sounds outlive buffers."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +28,19 @@ DEFAULT_VOLUME = [(0.0, 0.0), (0.004, 1.0), (0.2, 0.0)]
 def default_effect():
     """the reference's triple as SfxKit takes an effect: (modulator, carrier, volume), each (nodes, function)"""
     return ((DEFAULT_MODULATOR, smoothstep), (DEFAULT_CARRIER, smoothstep), (DEFAULT_VOLUME, smoothstep))
+
+
+# example_curve.zig:18-31 as (t, value) pairs
+CURVE_EXAMPLE_CARRIER = [(0.0, 440.0), (0.5, 880.0), (1.0, 110.0), (1.5, 660.0), (2.0, 330.0), (3.9, 20.0)]
+CURVE_EXAMPLE_MODULATOR = [(0.0, 110.0), (1.5, 55.0), (3.0, 220.0)]
+# the curve voice's note record: CurvePlayer.Params (example_curve.zig:36-39) without the shared sample rate, the effect, and the
+# note_on the dispatcher reads
+CURVE_NOTE_PARAMS = np.dtype([("rel_freq", "<f4"), ("effect", "<u4"), ("note_on", "<u4")])
+
+
+def curve_example_effect():
+    """the pair of curves of examples/example_curve.zig as SfxKit takes an effect; the curve voice reads no volume curve"""
+    return ((CURVE_EXAMPLE_MODULATOR, smoothstep), (CURVE_EXAMPLE_CARRIER, smoothstep), ([], smoothstep))
 
 
 def presets():
@@ -126,6 +140,68 @@ class LaserPlayer:
             return img.t()
         zang.mixdownGroups(span, self._mix, img, self.polyphony, zero_first=True, ctx=self.ctx)
         return self._mix[:, :frames]
+
+    def overflows(self):
+        return self.bank.overflows()
+
+    def close(self):
+        for o in (self.voices, self.bank):
+            if o is not None:
+                o.close()
+
+
+class CurvePlayer:
+    """N of the reference's curve examples (examples/example_curve.zig MainModule, :98-144) played live.  Per buffer: the pushed
+    impulses go through one LiveVoiceBank launch and one zh_curve_player_paint_spans renders every voice's sub-spans with each
+    impulse's rel_freq and effect (:126-129).  A sound runs for as long as its curves (the example's: 3.9 s): the voices carry it
+    from buffer to buffer."""
+
+    def __init__(self, ctx, n_players, kit, polyphony=1, sample_rate=48000, sync=False, max_impulses=None):
+        """`polyphony`: voices per player (the example has one CurvePlayer: 1, a new impulse restarts the sound).  `sync`: the
+        carrier's frequency image (the example's output_sync_oscilloscope) is painted too.  `max_impulses`: the most pushes one
+        buffer may carry over all players (default 33 per player: one more than their queues accept)."""
+        self.ctx, self.kit, self.n_players, self.polyphony = ctx, kit, int(n_players), int(polyphony)
+        self.sample_rate, self.sync = float(sample_rate), bool(sync)
+        self.n_voices = self.n_players * self.polyphony
+        self.bank = LiveVoiceBank(ctx, self.n_players, self.polyphony, CURVE_NOTE_PARAMS, CURVE_NOTE_PARAMS.fields["note_on"][1],
+                                  33 * self.n_players if max_impulses is None else int(max_impulses), rows=MAX_SPANS)
+        word = lambda name: CURVE_NOTE_PARAMS.fields[name][1] // 4
+        self._table = self.bank.script_table(MAX_SPANS, {"rel_freq": (word("rel_freq"), "f"), "effect": (word("effect"), "u")})
+        self.voices = mod.CurveVoice(self.n_voices, ctx)
+        self._params = mod.CurveVoice.Params(kit, self.sample_rate)   # every field has a span array
+        self._frames = 0
+
+    def push(self, player, frame, note_id, effect=0, rel_freq=1.0):
+        """keyEvent's iq.push (:135-138): scalars, or equal-length arrays in push order"""
+        rel_freq = np.atleast_1d(np.asarray(rel_freq, np.float32))
+        rec = np.zeros(max(len(rel_freq), np.atleast_1d(np.asarray(effect)).size), CURVE_NOTE_PARAMS)
+        rec["rel_freq"] = rel_freq
+        rec["effect"] = effect
+        rec["note_on"] = 1                                           # the dispatcher needs one; the sound has no note-off
+        self.bank.push(player, frame, note_id, rec)
+
+    def _reserve(self, frames):
+        if frames > self._frames:
+            self._image = self.ctx.image(frames, self.n_voices)
+            self._sync = self.ctx.image(frames, self.n_voices) if self.sync else None
+            self._mix = torch.zeros((self.n_players, frames), dtype=torch.float32, device=self.ctx.device)
+            self._frames = frames
+
+    def paint(self, frames):
+        """one buffer -> [n_players][frames] f32 on the device, or with sync=True (that, the frequency image [n_voices][frames])
+        (views of buffers the next call overwrites).  Every step is enqueued; nothing synchronises."""
+        self._reserve(frames)
+        span = zang.Span(0, frames)
+        self.bank.schedule(frames, MAX_SPANS)
+        img = self._image[:frames]
+        sync = self._sync[:frames] if self.sync else None
+        self.voices.paint_spans(span, [img, sync], None, self._params, self._table, zero_first=True)
+        if self.polyphony == 1:
+            out = img.t()
+        else:
+            zang.mixdownGroups(span, self._mix, img, self.polyphony, zero_first=True, ctx=self.ctx)
+            out = self._mix[:, :frames]
+        return (out, sync.t()) if self.sync else out
 
     def overflows(self):
         return self.bank.overflows()
