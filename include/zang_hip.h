@@ -1630,6 +1630,42 @@ ZH_API int zh_zscript_module_num_temps(zh_zscript *z, uint32_t i, uint32_t *num_
 ZH_API int zh_zscript_module_param(zh_zscript *z, uint32_t i, uint32_t p, char *name, size_t name_cap, char *kind, size_t kind_cap,
                                    char *enum_name, size_t enum_cap);
 
+/* ---------------------------------------------------------------- spectrum analyser (examples/common/fft.zig, examples/visual.zig)
+ * What the example harness does with every MainModule's output_visualize buffer, 1,024 frames at a time, for every voice of a
+ * [frame][voice] image in ONE kernel (csrc/spectrum.hip): the radix-2 FFT of fft.zig:3-60 on a workgroup's tile in LDS, then one of
+ * three epilogues.  Bit-identical to the reference, whose transform has three quirks that are kept:
+ *   - twiddles by recurrence: u_1, u_2 are rotated by (c, s) in f32 and (c, s) halved by sqrt per stage (:36-58); they are up to
+ *     3.6e-4 from exp(-2 pi i j / n) and the result about 3e-4 of max|X| from an exact FFT's.  No other FFT is bit-comparable.
+ *   - the three-multiply butterfly t2 = (re - im) * u_2; t1 = t2 + re * (u_1 - u_2); t2 = t2 + im * (u_1 + u_2) (:45-51), each
+ *     statement rounded in f32, nothing fused.
+ *   - both widgets read fft_real ONLY (visual.zig:269, :430): a sine exactly on bin 100 shows next to nothing at bin 100 (its energy
+ *     is in fft_imag), a cosine 0.7071069.
+ * DEFINED where the reference is not: a float-to-u32 cast saturates and NaN casts to 0 (the channel bytes of hslToRgb, the bin index
+ * of getFFTValue); height < 2 is refused (the reference divides by height - 1); n must be a power of two >= 2 (fftBitReverse
+ * underflows at 1).
+ * The twiddle pairs live in a table of the context, built and uploaded by the FIRST of these calls on it (that one call allocates
+ * and synchronises; inside a capture it returns ZH_ERR_UNSUPPORTED instead).  No later call allocates, copies or synchronises:
+ * all may be recorded into a graph.  Dispatch rows spectrum_tile / spectrum_stages pick the tile width and the schedule (same bits).
+ * ZH_ERR_INVALID: NULL arguments, n not a power of two in [2, 1024], rows outside an image, images of different voice counts or
+ * that overlap, out.frames < 512, height < 2, row_stride_pixels < voices.  Zero voices: ZH_OK, nothing launched. */
+/* fft.zig:26-58, host only, no device: the n - 1 pairs (u_1, u_2) the loops walk through, u[2 k] = u_1 and u[2 k + 1] = u_2; stage
+ * l1 = 1, 2, 4, ... contributes l1 pairs, in stage order, so the table of a smaller n is a prefix (1,023 pairs = 8 KiB at 1,024). */
+ZH_API int zh_fft_twiddles(float *u /*[2 * (n - 1)]*/, uint32_t n);
+/* fft(N, re, im) (:25-60) for every voice, in place on rows [frame_start, frame_start + n) of both images */
+ZH_API int zh_fft(zh_ctx *ctx, uint32_t n, uint32_t frame_start, zh_buf re, zh_buf im);
+/* DrawSpectrum.plot (visual.zig:257-280) on rows [frame_start, frame_start + 1024) of `samples`: out[k][v] = sqrt(|fft_real[k]| *
+ * (1 / 1024)) for k in [0, 512) -- assigned, not added; rows from 512 on are not touched.  `samples` is read once; there is no
+ * imaginary image and no scratch. */
+ZH_API int zh_spectrum_plot(zh_ctx *ctx, uint32_t frame_start, zh_buf samples, zh_buf out);
+/* The column DrawSpectrumFull.plot (visual.zig:411-452) draws: pixel i in [0, height) of voice v -- getFFTValue(i / (height - 1))
+ * (:141-159: position f * 511.5, or ((pow(10, f) - 1) / 9) * 511.5 when `logarithmic`; the blend of bins floor and min(511, floor +
+ * 1)) of fft_real, coloured hslToRgb(sqrt(|value| / 1024), 1, 0.5) (:88-125; 0xFF000000 | b << 16 | g << 8 | r, the bytes
+ * overlapping where the value exceeds 1,024) or 0xFFFF0000 for a NaN -- goes to pixels[(height - 1 - i) * row_stride_pixels + v],
+ * `pixels` a device pointer.  A spectrogram buffer is [height][width][voice]: pass pixels + drawindex * voices and row_stride_pixels =
+ * width * voices; the stores stay voice-contiguous. */
+ZH_API int zh_spectrum_column(zh_ctx *ctx, uint32_t frame_start, zh_buf samples, uint32_t *pixels, size_t row_stride_pixels,
+                              uint32_t height, int logarithmic);
+
 /* ---------------------------------------------------------------- event scheduling (host side; no GPU work)
  * The immediate caller of every paint: song / key events -> impulses ->
  * per-voice (span, params, note_id_changed) tuples.  A C++ restatement of src/zang/notes.zig and

@@ -457,6 +457,62 @@ public:
     }
 };
 
+// fft(N, re, im) of examples/common/fft.zig (:25-60) for every voice, in place on rows [frame_start, frame_start + n) of both images
+inline void fft(Context &c, uint32_t n, zh_buf re, zh_buf im, uint32_t frame_start = 0) { check(zh_fft(c.get(), n, frame_start, re, im), "fft"); }
+
+// DrawSpectrum.plot (examples/visual.zig:257-280) for n voices: fft_out as a [512][voice] image, assigned by every plot
+class Spectrum {
+    Context &ctx_;
+    Image out_;
+
+public:
+    Spectrum(Context &ctx, uint32_t n_voices) : ctx_(ctx), out_(ctx, n_voices, 512) { zero(ctx, Span{0, 512}, out_); }   // :245
+    const Image &plot(zh_buf samples, uint32_t frame_start = 0) {
+        check(zh_spectrum_plot(ctx_.get(), frame_start, samples, out_), "zh_spectrum_plot");
+        return out_;
+    }
+    const Image &out() const { return out_; }
+};
+
+// DrawSpectrumFull (examples/visual.zig:363-458) for n voices: a [height][width][voice] buffer of pixel words on the device, one
+// column per plot at drawindex, which wraps at width; a change of `logarithmic` zeroes the buffer and resets drawindex first
+class Spectrogram {
+    Context &ctx_;
+    uint32_t voices_, width_, height_, drawindex_ = 0;
+    bool logarithmic_ = false;
+    DeviceArray<uint32_t> buffer_;
+
+public:
+    Spectrogram(Context &ctx, uint32_t n_voices, uint32_t width, uint32_t height)
+        : ctx_(ctx), voices_(n_voices), width_(width), height_(height), buffer_(ctx, std::vector<uint32_t>((size_t)height * width * n_voices, 0u)) {
+        if (height < 2 || width < 1) throw Error(ZH_ERR_INVALID, "Spectrogram: height >= 2 and width >= 1");
+    }
+    uint32_t drawindex() const { return drawindex_; }
+    bool logarithmic() const { return logarithmic_; }
+    void plot(zh_buf samples, uint32_t frame_start, bool logarithmic) {                                                   // :411-452
+        if (logarithmic_ != logarithmic) {
+            logarithmic_ = logarithmic;
+            const std::vector<uint32_t> zeros(buffer_.size(), 0u);
+            check(zh_upload(ctx_.get(), buffer_.get(), zeros.data(), zeros.size() * sizeof(uint32_t)), "zh_upload");
+            drawindex_ = 0;
+        }
+        check(zh_spectrum_column(ctx_.get(), frame_start, samples, buffer_.get() + (size_t)drawindex_ * voices_, (size_t)width_ * voices_, height_,
+                                 logarithmic ? 1 : 0), "zh_spectrum_column");
+        if (++drawindex_ == width_) drawindex_ = 0;
+    }
+    std::vector<uint32_t> download() const { return buffer_.download(); }                     // [height][width][voice] as stored
+    // the picture in time order, as scrollBlit (:127-139) draws it: stored columns drawindex.. first, then ..drawindex
+    std::vector<uint32_t> scrolled() const {
+        const std::vector<uint32_t> b = buffer_.download();
+        std::vector<uint32_t> out(b.size());
+        for (uint32_t y = 0; y < height_; y++)
+            for (uint32_t x = 0; x < width_; x++)
+                for (uint32_t v = 0; v < voices_; v++)
+                    out[((size_t)y * width_ + x) * voices_ + v] = b[((size_t)y * width_ + (x + drawindex_) % width_) * voices_ + v];
+        return out;
+    }
+};
+
 // Instrument of examples/example_portamento.zig (:20-87) for n voices as one fused kernel: a sine whose frequency glides toward
 // the note's, times an envelope; the voice carries prev_note_on across sub-spans.  outputs[0] = the voice, outputs[1] = the
 // frequency image (a zh_buf{} whose ptr is NULL: not painted)

@@ -44,6 +44,7 @@ hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void *func, hipFuncAttribute, int value) { if (!func || value < 0) die("hipFuncSetAttribute without a kernel or with a negative value"); return hipSuccess; }
 const char *hipGetErrorString(hipError_t) { return "hip_stub error"; }
 hipError_t hipMalloc(void **p, size_t n) {
     *p = malloc(n ? n : 1);

@@ -11,5 +11,6 @@ abi.load()  # fail loudly if libzang_hip.so is missing or incomplete
 
 from . import zang, modules  # noqa: E402
 from .runtime import Context, default_context  # noqa: E402
+from .spectrum import Spectrum, Spectrogram  # noqa: E402
 
-__all__ = ["abi", "zang", "modules", "Context", "default_context"]
+__all__ = ["abi", "zang", "modules", "Context", "default_context", "Spectrum", "Spectrogram"]

@@ -597,6 +597,10 @@ SIGNATURES = {
     "zh_noise_set_state": (C.c_int, [vp, vp]),
     "zh_selftest_noise_jump": (C.c_int, [u64, u32]),
     "zh_noise_paint": (C.c_int, _paint(NoiseParams)),
+    "zh_fft_twiddles": (C.c_int, [P(f32), u32]),
+    "zh_fft": (C.c_int, [vp, u32, u32, Buf, Buf]),
+    "zh_spectrum_plot": (C.c_int, [vp, u32, Buf, Buf]),
+    "zh_spectrum_column": (C.c_int, [vp, u32, Buf, vp, C.c_size_t, u32, C.c_int]),
     "zh_envelope_create": (C.c_int, [vp, u32, P(vp)]),
     "zh_envelope_destroy": (C.c_int, [vp]),
     "zh_envelope_get_state": (C.c_int, [vp, vp]),

@@ -98,6 +98,7 @@ struct zh_ctx {
     bool co_plan_ok = true;
     uint32_t capture_launches = 0, co_plan_launches = 0;
     void *noise_jump;            // xoshiro256++ jump tables (noise_jump.hip), built on first use, freed with the context
+    void *fft_twiddles = nullptr;   // the spectrum analyser's twiddle pairs (spectrum.hip), the same
 };
 
 struct zh_graph {
@@ -160,7 +161,8 @@ enum { ZF_SINE_RANGES, ZF_NOISE_RANGES, ZF_ENVELOPE_RANGES, ZF_SAMPLER_RANGES, Z
        ZF_NICE_MIX_ROLL, ZF_NICE_MIX_WG_MIN, ZF_NF_PC_MAX, ZF_NF_RING_MAX, ZF_FILTER_PC_MAX, ZF_FILTER_PC16_MAX, ZF_FILTER_PC_CTL_MAX,
        ZF_PINK_PIPE_MAX, ZF_PINK_TAPS, ZF_ECHOES_PC_MAX, ZF_DELAY_FRAMES_MAX, ZF_FILTER_TP_MAX, ZF_NF_TP_MAX, ZF_NICE_TP_MAX,
        ZF_PINK_TP_MAX, ZF_ECHOES_TP_MAX, ZF_NICE_MIX_FMA, ZF_BASICS_ROWS_MIN, ZF_SCRIPT_PC, ZF_SCRIPT_PC_MAXV, ZF_NF_TP_PIPE_FRAMES, ZF_DISTORTION_ROWS_MIN, ZF_DISTORTION_RC, ZF_GRAPH_DIRECT,
-       ZF_STEREO_ECHOES_PC_MAX, ZF_LASER_UNIFORM_WALK, ZF_DETUNED_UNIFORM_WALK, ZF_COUNT };
+       ZF_STEREO_ECHOES_PC_MAX, ZF_LASER_UNIFORM_WALK, ZF_DETUNED_UNIFORM_WALK, ZF_SPECTRUM_TILE,
+       ZF_SPECTRUM_STAGES, ZF_COUNT };
 long zh_form(int id);
 bool zh_form_is_set(int id);                 // the row is overridden through ZH_FORMS
 uint32_t zh_range_frames(uint32_t V, uint32_t n, int form, uint32_t target_waves, uint32_t max_voices);

@@ -135,6 +135,7 @@ int zh_destroy(zh_ctx *ctx) { ZH_GUARD(ctx);
     if (ctx->mix_partials) hipFree(ctx->mix_partials);
     for (float *p : ctx->mix_retired) hipFree(p);
     if (ctx->noise_jump) hipFree(ctx->noise_jump);
+    if (ctx->fft_twiddles) hipFree(ctx->fft_twiddles);
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return ZH_OK;

@@ -67,6 +67,8 @@ const FormRow kForms[ZF_COUNT] = {
     /* ZF_STEREO_ECHOES_PC_MAX */ {"stereo_echoes_pc_max", 32768, "StereoEchoes: up to here loader / filter / writer waves (k_stereo_echoes_pc); StereoEchoes(15000), 1,024 frames, role waves against the walk: 253 / 318 us at 32,768 voices, 518 / 454 at 65,536 (profiles/r10)"},
     /* ZF_LASER_UNIFORM_WALK */ {"laser_uniform_walk", 0, "zh_laser_paint: 0 = its own kernel, no table walk (k_laser); 1 = k_laser_spans over a table of one sub-span per voice (the walk's cost, A/B)"},
     /* ZF_DETUNED_UNIFORM_WALK */ {"detuned_uniform_walk", 0, "zh_detuned_paint: 0 = its own kernel, no table walk (k_detuned); 1 = k_detuned_spans over a table of one sub-span per voice (the walk's cost, A/B)"},
+    /* ZF_SPECTRUM_TILE      */ {"spectrum_tile", 16, "zh_fft / zh_spectrum_plot / zh_spectrum_column: voices per workgroup tile of k_spectrum: 16 (128 KiB of LDS at 1,024 frames, one workgroup of 16 waves per CU: 740 us at 131,072 voices, 23.5 at 4,096) or 8 (64 KiB, two: 831 / 24.6; profiles/r25)"},
+    /* ZF_SPECTRUM_STAGES    */ {"spectrum_stages", 2, "... butterfly stages per pass over the tile: 2 (a lane's four points in registers, five barriers at 1,024 frames) or 1 (ten: 903 us at 131,072 voices against 740)"},
 };
 
 struct Overrides { bool set[ZF_COUNT]; long val[ZF_COUNT]; };
