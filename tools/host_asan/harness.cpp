@@ -1,6 +1,7 @@
 // harness.cpp -- random sequences through the C ABI against libzang_hip built host-only with ASan + UBSan over hip_stub.cpp
 // (tools/host_asan.sh): begin_capture (with and without ZH_CAPTURE_COALESCE), paints of flipper modules (PulseOsc / TriSawOsc in
-// table form, SineOsc as frame ranges), held-back batches (oscillators, stereo mixdowns), the pipelined Noise -> Filter recording,
+// table form, SineOsc as frame ranges; Envelope, Decimator and PMOsc: blocks of 4, 2 and 6 words per voice through the shared
+// create / destroy / get_state / set_state of csrc/state_block.hip.h), held-back batches (oscillators, stereo mixdowns), the pipelined Noise -> Filter recording,
 // eager paints between replays, end / launch / destroy in every order -- modules before their graphs, the context before its graphs.
 // Before them, once with no player and once with five: a live bank and each span-table stage (arp, subsong, merge) through create,
 // reserve, views, schedule, overflows and destroy (stage_passes).
@@ -18,7 +19,7 @@ static unsigned rnd() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return (u
 static unsigned pick(unsigned n) { return rnd() % n; }
 #define OK(x) do { int rc_ = (x); if (rc_ != ZH_OK) { fprintf(stderr, "%s:%d: %s -> %d\n", __FILE__, __LINE__, #x, rc_); exit(1); } } while (0)
 
-enum Kind { PULSE, TRISAW, SINE, NF, NICE, NKIND };
+enum Kind { PULSE, TRISAW, SINE, NF, NICE, ENV, DECIM, PMOSC, NKIND };
 struct Mod { Kind kind; void *h; unsigned V; float *freq, *color; bool painted; };
 struct Ctx {
     zh_ctx *c;
@@ -51,6 +52,9 @@ static void add_module(Ctx &cx) {
     case TRISAW: OK(zh_trisawosc_create(cx.c, m.V, (zh_trisawosc **)&m.h)); break;
     case SINE: OK(zh_sineosc_create(cx.c, m.V, (zh_sineosc **)&m.h)); break;
     case NF: OK(zh_noise_filter_create(cx.c, m.V, 7, (zh_noise_filter **)&m.h)); break;
+    case ENV: OK(zh_envelope_create(cx.c, m.V, (zh_envelope **)&m.h)); break;
+    case DECIM: OK(zh_decimator_create(cx.c, m.V, (zh_decimator **)&m.h)); break;
+    case PMOSC: OK(zh_pmosc_create(cx.c, m.V, f32p(m.color), (zh_pmosc **)&m.h)); break;
     default: OK(zh_nice_create(cx.c, m.V, f32p(m.color), (zh_nice **)&m.h)); break;
     }
     cx.mods.push_back(m);
@@ -62,6 +66,9 @@ static void drop_module(Ctx &cx, size_t i) {
     case TRISAW: OK(zh_trisawosc_destroy((zh_trisawosc *)m.h)); break;
     case SINE: OK(zh_sineosc_destroy((zh_sineosc *)m.h)); break;
     case NF: OK(zh_noise_filter_destroy((zh_noise_filter *)m.h)); break;
+    case ENV: OK(zh_envelope_destroy((zh_envelope *)m.h)); break;
+    case DECIM: OK(zh_decimator_destroy((zh_decimator *)m.h)); break;
+    case PMOSC: OK(zh_pmosc_destroy((zh_pmosc *)m.h)); break;
     default: OK(zh_nice_destroy((zh_nice *)m.h)); break;
     }
     OK(zh_free(cx.c, m.freq)); OK(zh_free(cx.c, m.color));
@@ -91,6 +98,13 @@ static void paint(Ctx &cx, Mod &m, const Fixed *fx = nullptr) {
     case NF: { zh_noise_filter_params p; memset(&p, 0, sizeof p); p.color = ZH_NOISE_WHITE; p.type = 1 + pick(5); p.cutoff = f32p(m.freq); p.res = f32c(0.5f);
         if (fx ? fx->tol : pick(3)) flags |= ZH_PAINT_TOLERANT;
         rc = zh_noise_filter_paint((zh_noise_filter *)m.h, s, e, &out, nullptr, boolc(0), &p, flags); break; }
+    case ENV: { zh_envelope_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.attack.tag = p.decay.tag = p.release.tag = ZH_CURVE_CUBED;
+        p.attack.duration = f32c(0.004f); p.decay.duration = f32p(m.color); p.release.duration = f32c(0.03f); p.sustain_volume = f32c(0.6f); p.note_on = boolc(pick(2));
+        rc = zh_envelope_paint((zh_envelope *)m.h, s, e, &out, nullptr, boolc(pick(2)), &p, flags); break; }
+    case DECIM: { zh_decimator_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.input = image(cx, m.V, 12); p.fake_sample_rate = f32p(m.freq);   // (image 12: never an output)
+        rc = zh_decimator_paint((zh_decimator *)m.h, s, e, &out, nullptr, boolc(0), &p, flags); break; }
+    case PMOSC: { zh_pmosc_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.freq = f32p(m.freq); p.note_on = boolc(pick(2));
+        rc = zh_pmosc_paint((zh_pmosc *)m.h, s, e, &out, nullptr, boolc(pick(2)), &p, flags); break; }
     default: { zh_nice_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.freq = f32p(m.freq); p.note_on = boolc(pick(2));
         static unsigned next_row = 0;
         const unsigned row = fx ? next_row++ % 31 : pick(31);
@@ -246,6 +260,9 @@ int main(int argc, char **argv) {
             else if (op < 92 && !cx.mods.empty()) {                      // state round trip of a flipper between paints and replays
                 Mod &m = cx.mods[pick((unsigned)cx.mods.size())];
                 if (m.kind == PULSE) { std::vector<zh_pulseosc_state> st(m.V); OK(zh_pulseosc_get_state((zh_pulseosc *)m.h, st.data())); OK(zh_pulseosc_set_state((zh_pulseosc *)m.h, st.data())); }
+                if (m.kind == ENV) { std::vector<zh_envelope_state> st(m.V); OK(zh_envelope_set_state((zh_envelope *)m.h, st.data())); OK(zh_envelope_get_state((zh_envelope *)m.h, st.data())); }
+                if (m.kind == DECIM) { std::vector<zh_decimator_state> st(m.V); OK(zh_decimator_set_state((zh_decimator *)m.h, st.data())); OK(zh_decimator_get_state((zh_decimator *)m.h, st.data())); }
+                if (m.kind == PMOSC) { std::vector<zh_pmosc_state> st(m.V); OK(zh_pmosc_set_state((zh_pmosc *)m.h, st.data())); OK(zh_pmosc_get_state((zh_pmosc *)m.h, st.data())); }
             }
             else OK(zh_sync(cx.c));
         }

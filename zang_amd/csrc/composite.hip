@@ -18,6 +18,7 @@
 #include "noise_jump.hip.h"
 #define ZH_FILTER_TP_NOISE 1
 #include "filter_tp.hip.h"
+#include "module_state.hip.h"
 #include <vector>
 #include <string.h>
 #include <stdlib.h>
@@ -54,8 +55,8 @@ struct zh_pmosc : zh_flipper {
     void view() {
         uint32_t *b = cnt[cur];
         const size_t N = n;
-        tc = reinterpret_cast<float *>(b); tm = reinterpret_cast<float *>(b + N); estate = b + 2 * N;
-        et = reinterpret_cast<float *>(b + 3 * N); elast = reinterpret_cast<float *>(b + 4 * N); estart = reinterpret_cast<float *>(b + 5 * N);
+        tc = reinterpret_cast<float *>(b + PM_CARRIER_T * N); tm = reinterpret_cast<float *>(b + PM_MODULATOR_T * N); estate = b + PM_ENV * N;
+        et = reinterpret_cast<float *>(estate + N); elast = reinterpret_cast<float *>(estate + 2 * N); estart = reinterpret_cast<float *>(estate + 3 * N);
     }
 };
 
@@ -1289,9 +1290,6 @@ __global__ void k_fill_u32(uint32_t *p, uint32_t n, uint32_t v) {
     if (i < n) p[i] = v;
 }
 
-template <typename T> static int up(zh_ctx *ctx, T *dev, const std::vector<T> &h) { return zh_upload(ctx, dev, h.data(), h.size() * sizeof(T)); }
-template <typename T> static int down(zh_ctx *ctx, std::vector<T> &h, const T *dev, size_t n) { h.resize(n); return zh_download(ctx, h.data(), dev, n * sizeof(T)); }
-
 static NiceArgs nice_args(zh_nice *m, const zh_nice_params *p, zh_bool nic) {
     NiceArgs a;
     a.color = m->color; a.cnt = m->cnt; a.fl = m->fl; a.fb = m->fb;
@@ -1311,7 +1309,7 @@ static void nice_free(zh_nice *m) {
     (void)hipFree(m->estate); (void)hipFree(m->et); (void)hipFree(m->elast); (void)hipFree(m->estart);
     (void)hipFree(m->tp);
 }
-static void pmosc_free(zh_pmosc *m) { (void)hipFree(m->release_duration); (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); }
+static void pmosc_free(zh_pmosc *m) { (void)hipFree(m->release_duration); flip_free(m); }
 
 extern "C" {
 
@@ -1350,13 +1348,13 @@ int zh_nice_get_state(zh_nice *m, zh_nice_state *host) { ZH_GUARD(m ? m->ctx : n
     if (!m || !host) return ZH_ERR_INVALID;
     std::vector<uint32_t> cnt, es;
     std::vector<float> l, b, t, lv, sv;
-    int rc = down(m->ctx, cnt, m->cnt, m->n);
-    if (!rc) rc = down(m->ctx, l, m->fl, m->n);
-    if (!rc) rc = down(m->ctx, b, m->fb, m->n);
-    if (!rc) rc = down(m->ctx, es, m->estate, m->n);
-    if (!rc) rc = down(m->ctx, t, m->et, m->n);
-    if (!rc) rc = down(m->ctx, lv, m->elast, m->n);
-    if (!rc) rc = down(m->ctx, sv, m->estart, m->n);
+    int rc = download_field(m->ctx, cnt, m->cnt, m->n);
+    if (!rc) rc = download_field(m->ctx, l, m->fl, m->n);
+    if (!rc) rc = download_field(m->ctx, b, m->fb, m->n);
+    if (!rc) rc = download_field(m->ctx, es, m->estate, m->n);
+    if (!rc) rc = download_field(m->ctx, t, m->et, m->n);
+    if (!rc) rc = download_field(m->ctx, lv, m->elast, m->n);
+    if (!rc) rc = download_field(m->ctx, sv, m->estart, m->n);
     if (rc) return rc;
     for (uint32_t v = 0; v < m->n; v++) {
         host[v].osc.cnt = cnt[v];
@@ -1374,13 +1372,13 @@ int zh_nice_set_state(zh_nice *m, const zh_nice_state *host) { ZH_GUARD(m ? m->c
         cnt[v] = host[v].osc.cnt; l[v] = host[v].flt.l; b[v] = host[v].flt.b;
         es[v] = host[v].env.state; t[v] = host[v].env.t; lv[v] = host[v].env.last_value; sv[v] = host[v].env.start;
     }
-    int rc = up(m->ctx, m->cnt, cnt);
-    if (!rc) rc = up(m->ctx, m->fl, l);
-    if (!rc) rc = up(m->ctx, m->fb, b);
-    if (!rc) rc = up(m->ctx, m->estate, es);
-    if (!rc) rc = up(m->ctx, m->et, t);
-    if (!rc) rc = up(m->ctx, m->elast, lv);
-    if (!rc) rc = up(m->ctx, m->estart, sv);
+    int rc = upload_field(m->ctx, m->cnt, cnt);
+    if (!rc) rc = upload_field(m->ctx, m->fl, l);
+    if (!rc) rc = upload_field(m->ctx, m->fb, b);
+    if (!rc) rc = upload_field(m->ctx, m->estate, es);
+    if (!rc) rc = upload_field(m->ctx, m->et, t);
+    if (!rc) rc = upload_field(m->ctx, m->elast, lv);
+    if (!rc) rc = upload_field(m->ctx, m->estart, sv);
     return rc;
 }
 int zh_nice_paint(zh_nice *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
@@ -1684,13 +1682,13 @@ int zh_noise_filter_get_state(zh_noise_filter *m, zh_noise_filter_state *host) {
     std::vector<uint64_t> s;
     std::vector<float> nb, l, b;
     for (int i = 0; i < 4; i++) {
-        int rc = down(m->ctx, s, m->s[i], m->n);
+        int rc = download_field(m->ctx, s, m->s[i], m->n);
         if (rc) return rc;
         for (uint32_t v = 0; v < m->n; v++) host[v].noise.r[i] = s[v];
     }
-    int rc = down(m->ctx, nb, m->nb, (size_t)7 * m->n);
-    if (!rc) rc = down(m->ctx, l, m->l, m->n);
-    if (!rc) rc = down(m->ctx, b, m->b, m->n);
+    int rc = download_field(m->ctx, nb, m->nb, (size_t)7 * m->n);
+    if (!rc) rc = download_field(m->ctx, l, m->l, m->n);
+    if (!rc) rc = download_field(m->ctx, b, m->b, m->n);
     if (rc) return rc;
     for (uint32_t v = 0; v < m->n; v++) {
         for (int j = 0; j < 7; j++) host[v].noise.b[j] = nb[(size_t)j * m->n + v];
@@ -1707,16 +1705,16 @@ int zh_noise_filter_set_state(zh_noise_filter *m, const zh_noise_filter_state *h
     std::vector<float> nb((size_t)7 * n), l(n), b(n);
     for (int i = 0; i < 4; i++) {
         for (uint32_t v = 0; v < n; v++) s[v] = host[v].noise.r[i];
-        int rc = up(m->ctx, m->s[i], s);
+        int rc = upload_field(m->ctx, m->s[i], s);
         if (rc) return rc;
     }
     for (uint32_t v = 0; v < n; v++) {
         for (int j = 0; j < 7; j++) nb[(size_t)j * n + v] = host[v].noise.b[j];
         l[v] = host[v].flt.l; b[v] = host[v].flt.b;
     }
-    int rc = up(m->ctx, m->nb, nb);
-    if (!rc) rc = up(m->ctx, m->l, l);
-    if (!rc) rc = up(m->ctx, m->b, b);
+    int rc = upload_field(m->ctx, m->nb, nb);
+    if (!rc) rc = upload_field(m->ctx, m->l, l);
+    if (!rc) rc = upload_field(m->ctx, m->b, b);
     return rc;
 }
 int zh_noise_filter_paint(zh_noise_filter *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
@@ -1886,17 +1884,11 @@ int zh_pmosc_create(zh_ctx *ctx, uint32_t n, zh_f32 release_duration, zh_pmosc *
     if (!ctx || !out) return ZH_ERR_INVALID;
     zh_pmosc *m = new (std::nothrow) zh_pmosc();
     if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0; m->words = 6;
     m->release_duration = nullptr;
-    int rc = dev_alloc(&m->release_duration, n);
-    if (!rc) rc = dev_alloc(&m->cnt[0], (size_t)6 * n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], (size_t)6 * n);
+    int rc = flip_alloc(ctx, m, n, PmoscLayout::kWords);
+    if (!rc) rc = dev_alloc(&m->release_duration, n);
     if (rc) { pmosc_free(m); delete m; return rc; }
-    if (n) {
-        hipStream_t st = ctx->stream;
-        ZH_LAUNCH(k_fill_f32, dim3((n + 255) / 256), dim3(256), 0, st, m->release_duration, n, mk_f32(release_duration));
-        for (int b = 0; b < 2; b++) { hipError_t e = hipMemsetAsync(m->cnt[b], 0, (size_t)6 * n * 4, st); if (e != hipSuccess) { pmosc_free(m); delete m; return (int)e; } }
-    }
+    if (n) ZH_LAUNCH(k_fill_f32, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, m->release_duration, n, mk_f32(release_duration));
     m->view();
     zh_flipper_register(m);
     *out = m;
@@ -1911,40 +1903,12 @@ int zh_pmosc_destroy(zh_pmosc *m) { ZH_GUARD(m ? m->ctx : nullptr);
     return ZH_OK;
 }
 int zh_pmosc_get_state(zh_pmosc *m, zh_pmosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    m->view();
-    std::vector<uint32_t> es;
-    std::vector<float> tc, tm, t, lv, sv;
-    int rc = down(m->ctx, tc, m->tc, m->n);
-    if (!rc) rc = down(m->ctx, tm, m->tm, m->n);
-    if (!rc) rc = down(m->ctx, es, m->estate, m->n);
-    if (!rc) rc = down(m->ctx, t, m->et, m->n);
-    if (!rc) rc = down(m->ctx, lv, m->elast, m->n);
-    if (!rc) rc = down(m->ctx, sv, m->estart, m->n);
-    if (rc) return rc;
-    for (uint32_t v = 0; v < m->n; v++) {
-        host[v].carrier.t = tc[v]; host[v].modulator.t = tm[v];
-        host[v].env = zh_envelope_state{es[v], t[v], lv[v], sv[v]};
-    }
-    return ZH_OK;
+    if (m) m->view();
+    return flip_get_state<PmoscLayout>(m, host);
 }
 int zh_pmosc_set_state(zh_pmosc *m, const zh_pmosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    m->view();
-    const uint32_t n = m->n;
-    std::vector<uint32_t> es(n);
-    std::vector<float> tc(n), tm(n), t(n), lv(n), sv(n);
-    for (uint32_t v = 0; v < n; v++) {
-        tc[v] = host[v].carrier.t; tm[v] = host[v].modulator.t;
-        es[v] = host[v].env.state; t[v] = host[v].env.t; lv[v] = host[v].env.last_value; sv[v] = host[v].env.start;
-    }
-    int rc = up(m->ctx, m->tc, tc);
-    if (!rc) rc = up(m->ctx, m->tm, tm);
-    if (!rc) rc = up(m->ctx, m->estate, es);
-    if (!rc) rc = up(m->ctx, m->et, t);
-    if (!rc) rc = up(m->ctx, m->elast, lv);
-    if (!rc) rc = up(m->ctx, m->estart, sv);
-    return rc;
+    if (m) m->view();
+    return flip_set_state<PmoscLayout>(m, host);
 }
 int zh_pmosc_paint(zh_pmosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                    zh_bool note_id_changed, const zh_pmosc_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);

@@ -13,20 +13,20 @@
 
 // ---- the state's layout ------------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of zh_curve_player_state (example_curve.zig:41-44); a Curve's four words are
-// t, current_song_note, current_song_note_offset, next_song_note (lz_pack_curve)
+// t, current_song_note, current_song_note_offset, next_song_note (curve_pack)
 enum { CP_CARRIER_CURVE = 0, CP_CARRIER_T = 4, CP_MODULATOR_CURVE = 5, CP_MODULATOR_T = 9, kCurvePlayerState = 10 };
 
 // voice v of n: struct -> rows (w = uint32_t[kCurvePlayerState * n]) and back
 inline void cp_pack(const zh_curve_player_state &s, uint32_t *w, size_t n, size_t v) {
-    lz_pack_curve(s.carrier_curve, w + (size_t)CP_CARRIER_CURVE * n + v, n);
+    curve_pack(s.carrier_curve, w + (size_t)CP_CARRIER_CURVE * n + v, n);
     w[(size_t)CP_CARRIER_T * n + v] = zh_f32_bits(s.carrier.t);
-    lz_pack_curve(s.modulator_curve, w + (size_t)CP_MODULATOR_CURVE * n + v, n);
+    curve_pack(s.modulator_curve, w + (size_t)CP_MODULATOR_CURVE * n + v, n);
     w[(size_t)CP_MODULATOR_T * n + v] = zh_f32_bits(s.modulator.t);
 }
 inline void cp_unpack(zh_curve_player_state &s, const uint32_t *w, size_t n, size_t v) {
-    s.carrier_curve = lz_unpack_curve(w + (size_t)CP_CARRIER_CURVE * n + v, n);
+    s.carrier_curve = curve_unpack(w + (size_t)CP_CARRIER_CURVE * n + v, n);
     s.carrier.t = zh_bits_f32(w[(size_t)CP_CARRIER_T * n + v]);
-    s.modulator_curve = lz_unpack_curve(w + (size_t)CP_MODULATOR_CURVE * n + v, n);
+    s.modulator_curve = curve_unpack(w + (size_t)CP_MODULATOR_CURVE * n + v, n);
     s.modulator.t = zh_bits_f32(w[(size_t)CP_MODULATOR_T * n + v]);
 }
 using CurvePlayerLayout = VoiceLayout<zh_curve_player_state, kCurvePlayerState, cp_pack, cp_unpack>;

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 // ---- the state's layout ------------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of zh_detuned_state; the generator's four u64 as (low, high) pairs.  The taps of
@@ -23,8 +24,7 @@ inline void ds_pack(const zh_detuned_state &s, uint32_t *w, size_t n, size_t v) 
     }
     w[(size_t)DS_NF_L * n + v] = zh_f32_bits(s.noise_filter.l); w[(size_t)DS_NF_B * n + v] = zh_f32_bits(s.noise_filter.b);
     w[(size_t)DS_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)DS_OSC_T * n + v] = zh_f32_bits(s.osc.t);
-    w[(size_t)DS_ENV_STATE * n + v] = s.env.state; w[(size_t)DS_ENV_T * n + v] = zh_f32_bits(s.env.t);
-    w[(size_t)DS_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)DS_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    env_pack(s.env, w + (size_t)DS_ENV_STATE * n + v, n);
     w[(size_t)DS_MF_L * n + v] = zh_f32_bits(s.main_filter.l); w[(size_t)DS_MF_B * n + v] = zh_f32_bits(s.main_filter.b);
 }
 inline void ds_unpack(zh_detuned_state &s, const uint32_t *w, size_t n, size_t v) {
@@ -33,8 +33,7 @@ inline void ds_unpack(zh_detuned_state &s, const uint32_t *w, size_t n, size_t v
         s.noise.r[j] = (uint64_t)w[(size_t)(DS_RNG + 2 * j) * n + v] | ((uint64_t)w[(size_t)(DS_RNG + 2 * j + 1) * n + v] << 32);
     s.noise_filter.l = zh_bits_f32(w[(size_t)DS_NF_L * n + v]); s.noise_filter.b = zh_bits_f32(w[(size_t)DS_NF_B * n + v]);
     s.osc.cnt = w[(size_t)DS_OSC_CNT * n + v]; s.osc.t = zh_bits_f32(w[(size_t)DS_OSC_T * n + v]);
-    s.env.state = w[(size_t)DS_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)DS_ENV_T * n + v]);
-    s.env.last_value = zh_bits_f32(w[(size_t)DS_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)DS_ENV_START * n + v]);
+    s.env = env_unpack(w + (size_t)DS_ENV_STATE * n + v, n);
     s.main_filter.l = zh_bits_f32(w[(size_t)DS_MF_L * n + v]); s.main_filter.b = zh_bits_f32(w[(size_t)DS_MF_B * n + v]);
 }
 using DetunedLayout = VoiceLayout<zh_detuned_state, kDetunedState, ds_pack, ds_unpack>;

@@ -12,19 +12,18 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 enum { DL_OSC_CNT = 0, DL_OSC_T, DL_ENV_STATE, DL_ENV_T, DL_ENV_LAST, DL_ENV_START, kDualState };   // words per voice, [word][voice]
 
 inline void dl_pack(const zh_dual_state &s, uint32_t *w, size_t n, size_t v) {
     w[(size_t)DL_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)DL_OSC_T * n + v] = zh_f32_bits(s.osc.t);
-    w[(size_t)DL_ENV_STATE * n + v] = s.env.state; w[(size_t)DL_ENV_T * n + v] = zh_f32_bits(s.env.t);
-    w[(size_t)DL_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)DL_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    env_pack(s.env, w + (size_t)DL_ENV_STATE * n + v, n);
 }
 inline void dl_unpack(zh_dual_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
     s.osc.cnt = w[(size_t)DL_OSC_CNT * n + v]; s.osc.t = zh_bits_f32(w[(size_t)DL_OSC_T * n + v]);
-    s.env.state = w[(size_t)DL_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)DL_ENV_T * n + v]);
-    s.env.last_value = zh_bits_f32(w[(size_t)DL_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)DL_ENV_START * n + v]);
+    s.env = env_unpack(w + (size_t)DL_ENV_STATE * n + v, n);
 }
 using DualLayout = VoiceLayout<zh_dual_state, kDualState, dl_pack, dl_unpack>;
 

@@ -6,7 +6,6 @@
 // tolerant form.
 #include "common.hip.h"
 #include "fm.hip.h"
-#include "span_voice.hip.h"   // zh_f32_bits / zh_bits_f32
 #include <vector>
 #include <string.h>
 
@@ -136,10 +135,9 @@ int zh_fm_create(zh_ctx *ctx, uint32_t n, uint32_t group, zh_fm **out) { ZH_GUAR
     if (!m) return ZH_ERR_INVALID;
     m->ctx = ctx; m->n = n; m->group = group; m->ni = (uint32_t)(((uint64_t)n + group - 1) / group);
     m->state = nullptr; m->tab = nullptr; m->patch = nullptr;
-    int rc = dev_alloc(&m->state, (size_t)kFmState * n);
+    int rc = dev_alloc_zeroed(ctx, &m->state, (size_t)kFmState * n);
     if (!rc) rc = dev_alloc(&m->tab, (size_t)kFmConsts * m->ni);
     if (!rc) rc = dev_alloc(&m->patch, (size_t)ZH_FM_PATCH_VALUES * m->ni);
-    if (!rc && n) { hipError_t e = hipMemsetAsync(m->state, 0, (size_t)kFmState * n * 4, ctx->stream); if (e != hipSuccess) rc = (int)e; }
     if (!rc) {
         zh_fm_patch d;
         memcpy(d.value, kFmDefault, sizeof(kFmDefault));
@@ -164,35 +162,10 @@ int zh_fm_set_patches(zh_fm *m, const zh_fm_patch *patches, uint32_t n_patches) 
 }
 
 int zh_fm_get_state(zh_fm *m, zh_fm_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)kFmState * n);
-    int rc = zh_download(m->ctx, w.data(), m->state, w.size() * 4);
-    if (rc) return rc;
-    const auto f = zh_bits_f32;
-    for (size_t v = 0; v < n; v++)
-        for (int op = 0; op < 2; op++) {
-            const uint32_t *s = w.data() + (size_t)op * FMS_OP * n + v;
-            zh_fm_op_state &o = op ? host[v].carrier : host[v].modulator;
-            o.t = f(s[FMS_T * n]); o.feedback1 = f(s[FMS_FB1 * n]); o.feedback2 = f(s[FMS_FB2 * n]); o.reserved = 0;
-            o.env = zh_envelope_state{s[FMS_ESTATE * n], f(s[FMS_ET * n]), f(s[FMS_ELAST * n]), f(s[FMS_ESTART * n])};
-        }
-    return ZH_OK;
+    return m && host ? block_get_state<FmLayout>(m->ctx, m->state, m->n, host) : ZH_ERR_INVALID;
 }
-
 int zh_fm_set_state(zh_fm *m, const zh_fm_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)kFmState * n);
-    const auto u = zh_f32_bits;
-    for (size_t v = 0; v < n; v++)
-        for (int op = 0; op < 2; op++) {
-            uint32_t *s = w.data() + (size_t)op * FMS_OP * n + v;
-            const zh_fm_op_state &o = op ? host[v].carrier : host[v].modulator;
-            s[FMS_T * n] = u(o.t); s[FMS_FB1 * n] = u(o.feedback1); s[FMS_FB2 * n] = u(o.feedback2);
-            s[FMS_ESTATE * n] = o.env.state; s[FMS_ET * n] = u(o.env.t); s[FMS_ELAST * n] = u(o.env.last_value); s[FMS_ESTART * n] = u(o.env.start);
-        }
-    return zh_upload(m->ctx, m->state, w.data(), w.size() * 4);
+    return m && host ? block_set_state<FmLayout>(m->ctx, m->state, m->n, host) : ZH_ERR_INVALID;
 }
 
 // the checks both paints share; on ZH_OK `flags` has lost ZH_PAINT_ZERO_FIRST where an LFO image overlaps the output (zeroed here)

@@ -6,7 +6,35 @@
 // The 22 discrete patch values (:375-398) become numbers ONCE (fm.hip k_fm_patch -> a constants table, one row per instrument);
 // a paint only loads its instrument's row.  Waveform, algorithm and feedback are per lane at run time: voices with different
 // patches share a launch.
+// Above the lanes, as plain C++ (tests/cpp/module_state_host.cpp): the state's rows and FmLayout, zh_fm_state <-> those rows.
 #pragma once
+#include "module_state.hip.h"
+
+// words of state per voice, [kFmState][n_voices]; an operator's seven, modulator first
+enum { FMS_T = 0, FMS_FB1, FMS_FB2, FMS_ESTATE, FMS_ET, FMS_ELAST, FMS_ESTART, FMS_OP = 7, kFmState = 14 };
+static_assert(FMS_ET == FMS_ESTATE + 1 && FMS_ELAST == FMS_ESTATE + 2 && FMS_ESTART == FMS_ESTATE + 3, "env_pack's rows");
+
+// voice v of n: struct -> rows (w = uint32_t[kFmState * n]) and back; `reserved` is no row and reads as 0
+inline void fm_pack(const zh_fm_state &st, uint32_t *w, size_t n, size_t v) {
+    for (int op = 0; op < 2; op++) {
+        uint32_t *s = w + (size_t)op * FMS_OP * n + v;
+        const zh_fm_op_state &o = op ? st.carrier : st.modulator;
+        s[(size_t)FMS_T * n] = zh_f32_bits(o.t); s[(size_t)FMS_FB1 * n] = zh_f32_bits(o.feedback1); s[(size_t)FMS_FB2 * n] = zh_f32_bits(o.feedback2);
+        env_pack(o.env, s + (size_t)FMS_ESTATE * n, n);
+    }
+}
+inline void fm_unpack(zh_fm_state &st, const uint32_t *w, size_t n, size_t v) {
+    for (int op = 0; op < 2; op++) {
+        const uint32_t *s = w + (size_t)op * FMS_OP * n + v;
+        zh_fm_op_state &o = op ? st.carrier : st.modulator;
+        o.t = zh_bits_f32(s[(size_t)FMS_T * n]); o.feedback1 = zh_bits_f32(s[(size_t)FMS_FB1 * n]); o.feedback2 = zh_bits_f32(s[(size_t)FMS_FB2 * n]);
+        o.reserved = 0;
+        o.env = env_unpack(s + (size_t)FMS_ESTATE * n, n);
+    }
+}
+using FmLayout = VoiceLayout<zh_fm_state, kFmState, fm_pack, fm_unpack>;
+
+#if defined(__HIPCC__)
 #include "common.hip.h"
 #include "zmath.hip.h"
 #include "seq.hip.h"
@@ -18,8 +46,6 @@ enum { FMC_FREQ_MUL = 0, FMC_VOLUME, FMC_ATTACK, FMC_DECAY, FMC_SUSTAIN, FMC_REL
        FMC_FEEDBACK = 16,          // the modulator's feedback amount (:193-203); the carrier's is always 0 (:346)
        FMC_BITS = 17,              // algorithm | modulator waveform << 1 | carrier waveform << 3
        kFmConsts = 18 };
-// words of state per voice, [kFmState][n_voices]; an operator's seven, modulator first
-enum { FMS_T = 0, FMS_FB1, FMS_FB2, FMS_ESTATE, FMS_ET, FMS_ELAST, FMS_ESTART, FMS_OP = 7, kFmState = 14 };
 
 #ifndef ZH_FM_CHUNK
 #define ZH_FM_CHUNK 4
@@ -243,3 +269,4 @@ __device__ __forceinline__ void fm_paint_frames(FMLane &n, const Img &out, uint3
         });
     }
 }
+#endif   // __HIPCC__

@@ -8,32 +8,27 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 // ---- the state's layout ------------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of zh_laser_state (example_laser.zig:51-55); a Curve's four words are
-// t, current_song_note, current_song_note_offset, next_song_note
+// t, current_song_note, current_song_note_offset, next_song_note (module_state.hip.h curve_pack)
 enum { LS_CARRIER_CURVE = 0, LS_CARRIER_T = 4, LS_MODULATOR_CURVE = 5, LS_MODULATOR_T = 9, LS_VOLUME_CURVE = 10, kLaserState = 14 };
 
-inline void lz_pack_curve(const zh_curve_module_state &c, uint32_t *s, size_t n) {
-    s[0] = zh_f32_bits(c.t); s[n] = c.current_song_note; s[2 * n] = (uint32_t)c.current_song_note_offset; s[3 * n] = c.next_song_note;
-}
-inline zh_curve_module_state lz_unpack_curve(const uint32_t *s, size_t n) {
-    return zh_curve_module_state{zh_bits_f32(s[0]), s[n], (int32_t)s[2 * n], s[3 * n]};
-}
 // voice v of n: struct -> rows (w = uint32_t[kLaserState * n]) and back
 inline void lz_pack(const zh_laser_state &s, uint32_t *w, size_t n, size_t v) {
-    lz_pack_curve(s.carrier_curve, w + (size_t)LS_CARRIER_CURVE * n + v, n);
+    curve_pack(s.carrier_curve, w + (size_t)LS_CARRIER_CURVE * n + v, n);
     w[(size_t)LS_CARRIER_T * n + v] = zh_f32_bits(s.carrier.t);
-    lz_pack_curve(s.modulator_curve, w + (size_t)LS_MODULATOR_CURVE * n + v, n);
+    curve_pack(s.modulator_curve, w + (size_t)LS_MODULATOR_CURVE * n + v, n);
     w[(size_t)LS_MODULATOR_T * n + v] = zh_f32_bits(s.modulator.t);
-    lz_pack_curve(s.volume_curve, w + (size_t)LS_VOLUME_CURVE * n + v, n);
+    curve_pack(s.volume_curve, w + (size_t)LS_VOLUME_CURVE * n + v, n);
 }
 inline void lz_unpack(zh_laser_state &s, const uint32_t *w, size_t n, size_t v) {
-    s.carrier_curve = lz_unpack_curve(w + (size_t)LS_CARRIER_CURVE * n + v, n);
+    s.carrier_curve = curve_unpack(w + (size_t)LS_CARRIER_CURVE * n + v, n);
     s.carrier.t = zh_bits_f32(w[(size_t)LS_CARRIER_T * n + v]);
-    s.modulator_curve = lz_unpack_curve(w + (size_t)LS_MODULATOR_CURVE * n + v, n);
+    s.modulator_curve = curve_unpack(w + (size_t)LS_MODULATOR_CURVE * n + v, n);
     s.modulator.t = zh_bits_f32(w[(size_t)LS_MODULATOR_T * n + v]);
-    s.volume_curve = lz_unpack_curve(w + (size_t)LS_VOLUME_CURVE * n + v, n);
+    s.volume_curve = curve_unpack(w + (size_t)LS_VOLUME_CURVE * n + v, n);
 }
 using LaserLayout = VoiceLayout<zh_laser_state, kLaserState, lz_pack, lz_unpack>;
 

@@ -15,6 +15,7 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 // ---- the states' layouts -----------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of the structs
@@ -23,19 +24,15 @@ enum { VS_VIB_T = 0, VS_OSC_CNT, kVibratoState };
 
 // voice v of n: struct -> rows (w = uint32_t[kPortaState * n]) and back
 inline void ps_pack(const zh_porta_state &s, uint32_t *w, size_t n, size_t v) {
-    w[(size_t)PS_PORTA_T * n + v] = zh_f32_bits(s.porta.t); w[(size_t)PS_PORTA_LAST * n + v] = zh_f32_bits(s.porta.last_value);
-    w[(size_t)PS_PORTA_START * n + v] = zh_f32_bits(s.porta.start);
-    w[(size_t)PS_ENV_STATE * n + v] = s.env.state; w[(size_t)PS_ENV_T * n + v] = zh_f32_bits(s.env.t);
-    w[(size_t)PS_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)PS_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    porta_pack(s.porta, w + (size_t)PS_PORTA_T * n + v, n);
+    env_pack(s.env, w + (size_t)PS_ENV_STATE * n + v, n);
     w[(size_t)PS_OSC_T * n + v] = zh_f32_bits(s.osc.t);
     w[(size_t)PS_PREV_NOTE_ON * n + v] = s.prev_note_on;
 }
 inline void ps_unpack(zh_porta_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
-    s.porta.t = zh_bits_f32(w[(size_t)PS_PORTA_T * n + v]); s.porta.last_value = zh_bits_f32(w[(size_t)PS_PORTA_LAST * n + v]);
-    s.porta.start = zh_bits_f32(w[(size_t)PS_PORTA_START * n + v]);
-    s.env.state = w[(size_t)PS_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)PS_ENV_T * n + v]);
-    s.env.last_value = zh_bits_f32(w[(size_t)PS_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)PS_ENV_START * n + v]);
+    s.porta = porta_unpack(w + (size_t)PS_PORTA_T * n + v, n);
+    s.env = env_unpack(w + (size_t)PS_ENV_STATE * n + v, n);
     s.osc.t = zh_bits_f32(w[(size_t)PS_OSC_T * n + v]);
     s.prev_note_on = w[(size_t)PS_PREV_NOTE_ON * n + v];
 }

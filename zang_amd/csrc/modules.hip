@@ -18,15 +18,8 @@
 #include "sample_kit.hip.h"
 #define ZH_FILTER_TP_PINK 1
 #include "filter_tp.hip.h"
+#include "module_state.hip.h"
 #include <vector>
-
-template <typename T> static int upload_field(zh_ctx *ctx, T *dev, const std::vector<T> &h) {
-    return zh_upload(ctx, dev, h.data(), h.size() * sizeof(T));
-}
-template <typename T> static int download_field(zh_ctx *ctx, std::vector<T> &h, const T *dev, size_t n) {
-    h.resize(n);
-    return zh_download(ctx, h.data(), dev, n * sizeof(T));
-}
 
 // =================================================================== SineOsc
 // The phase `t` is double-buffered like the chunked oscillators' counters (zh_flipper: a captured graph bakes both pointers
@@ -1393,43 +1386,16 @@ static EnvParamsP mk_env_params(const zh_envelope_params *p) {
                       mk_f32(p->decay.duration), mk_f32(p->release.duration), mk_f32(p->sustain_volume), mk_bool(p->note_on)};
 }
 
-// shared by the modules whose state is one double-buffered 32-bit word per voice (zh_sineosc, zh_sampler)
-template <class M> static int flip1_create(zh_ctx *ctx, uint32_t n, M **out) {
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    M *m = new (std::nothrow) M();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0;
-    int rc = dev_alloc(&m->cnt[0], n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], n);
-    if (!rc && n) rc = (int)hipMemsetAsync(m->cnt[0], 0, (size_t)n * 4, ctx->stream);   // init(): 0.0
-    if (!rc && n) rc = (int)hipMemsetAsync(m->cnt[1], 0, (size_t)n * 4, ctx->stream);
-    if (rc) { (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); delete m; return rc; }
-    zh_flipper_register(m);
-    *out = m;
-    return ZH_OK;
-}
-template <class M> static int flip1_destroy(M *m) {
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    zh_flipper_unregister(m);
-    (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]);
-    delete m;
-    return ZH_OK;
-}
-
 extern "C" {
 
+// The create / destroy / get_state / set_state of the modules that are a zh_flipper and nothing else: state_block.hip.h over
+// the module's Layout (module_state.hip.h).
+
 // ------------------------------------------------------------------ SineOsc
-int zh_sineosc_create(zh_ctx *ctx, uint32_t n, zh_sineosc **out) { ZH_GUARD(ctx); return flip1_create(ctx, n, out); }   // init(): t = 0 (SineOsc.zig:18-22)
-int zh_sineosc_destroy(zh_sineosc *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip1_destroy(m); }
-int zh_sineosc_get_state(zh_sineosc *m, zh_sineosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_download(m->ctx, host, m->t(), (size_t)m->n * 4);
-}
-int zh_sineosc_set_state(zh_sineosc *m, const zh_sineosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_upload(m->ctx, m->t(), host, (size_t)m->n * 4);
-}
+int zh_sineosc_create(zh_ctx *ctx, uint32_t n, zh_sineosc **out) { ZH_GUARD(ctx); return flip_create<SineOscLayout>(ctx, n, out); }   // init(): t = 0 (SineOsc.zig:18-22)
+int zh_sineosc_destroy(zh_sineosc *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_sineosc_get_state(zh_sineosc *m, zh_sineosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<SineOscLayout>(m, host); }
+int zh_sineosc_set_state(zh_sineosc *m, const zh_sineosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<SineOscLayout>(m, host); }
 int zh_sineosc_paint(zh_sineosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                      zh_bool note_id_changed, const zh_sineosc_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps; (void)note_id_changed;                                            // SineOsc.zig:32-33
@@ -1659,51 +1625,10 @@ int zh_noise_paint(zh_noise *m, uint32_t start, uint32_t end, const zh_buf *outp
 }
 
 // ------------------------------------------------------------------ Envelope
-int zh_envelope_create(zh_ctx *ctx, uint32_t n, zh_envelope **out) { ZH_GUARD(ctx);
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    zh_envelope *m = new (std::nothrow) zh_envelope();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0; m->words = 4;
-    int rc = dev_alloc(&m->cnt[0], (size_t)4 * n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], (size_t)4 * n);
-    for (int b = 0; b < 2 && !rc && n; b++) rc = (int)hipMemsetAsync(m->cnt[b], 0, (size_t)4 * n * 4, ctx->stream);   // init() :26-31: idle, painter zeros
-    if (rc) { (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); delete m; return rc; }
-    zh_flipper_register(m);
-    *out = m;
-    return ZH_OK;
-}
-int zh_envelope_destroy(zh_envelope *m) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    zh_flipper_unregister(m);
-    (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]);
-    delete m;
-    return ZH_OK;
-}
-int zh_envelope_get_state(zh_envelope *m, zh_envelope_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    std::vector<uint32_t> w;
-    int rc = download_field(m->ctx, w, m->cnt[m->cur], (size_t)4 * m->n);
-    if (rc) return rc;
-    const size_t n = m->n;
-    for (uint32_t v = 0; v < m->n; v++) {
-        zh_envelope_state e;
-        e.state = w[v];
-        memcpy(&e.t, &w[n + v], 4); memcpy(&e.last_value, &w[2 * n + v], 4); memcpy(&e.start, &w[3 * n + v], 4);
-        host[v] = e;
-    }
-    return ZH_OK;
-}
-int zh_envelope_set_state(zh_envelope *m, const zh_envelope_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w(4 * n);
-    for (uint32_t v = 0; v < m->n; v++) {
-        w[v] = host[v].state;
-        memcpy(&w[n + v], &host[v].t, 4); memcpy(&w[2 * n + v], &host[v].last_value, 4); memcpy(&w[3 * n + v], &host[v].start, 4);
-    }
-    return upload_field(m->ctx, m->cnt[m->cur], w);
-}
+int zh_envelope_create(zh_ctx *ctx, uint32_t n, zh_envelope **out) { ZH_GUARD(ctx); return flip_create<EnvelopeLayout>(ctx, n, out); }   // init() :26-31: idle, painter zeros
+int zh_envelope_destroy(zh_envelope *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_envelope_get_state(zh_envelope *m, zh_envelope_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<EnvelopeLayout>(m, host); }
+int zh_envelope_set_state(zh_envelope *m, const zh_envelope_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<EnvelopeLayout>(m, host); }
 int zh_envelope_paint(zh_envelope *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                       zh_bool note_id_changed, const zh_envelope_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
@@ -1991,16 +1916,10 @@ int zh_sample_kit_sample(const zh_sample_kit *kit, uint32_t i, zh_sample *out) {
     return ZH_OK;
 }
 
-int zh_sampler_create(zh_ctx *ctx, uint32_t n, zh_sampler **out) { ZH_GUARD(ctx); return flip1_create(ctx, n, out); }   // init() :71-75
-int zh_sampler_destroy(zh_sampler *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip1_destroy(m); }
-int zh_sampler_get_state(zh_sampler *m, zh_sampler_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_download(m->ctx, host, m->t(), (size_t)m->n * 4);
-}
-int zh_sampler_set_state(zh_sampler *m, const zh_sampler_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_upload(m->ctx, m->t(), host, (size_t)m->n * 4);
-}
+int zh_sampler_create(zh_ctx *ctx, uint32_t n, zh_sampler **out) { ZH_GUARD(ctx); return flip_create<SamplerLayout>(ctx, n, out); }   // init() :71-75
+int zh_sampler_destroy(zh_sampler *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_sampler_get_state(zh_sampler *m, zh_sampler_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<SamplerLayout>(m, host); }
+int zh_sampler_set_state(zh_sampler *m, const zh_sampler_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<SamplerLayout>(m, host); }
 int zh_sampler_paint(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                      zh_bool note_id_changed, const zh_sampler_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
@@ -2046,45 +1965,12 @@ int zh_sampler_paint(zh_sampler *m, uint32_t start, uint32_t end, const zh_buf *
 
 // ------------------------------------------------------------------ Decimator
 int zh_decimator_create(zh_ctx *ctx, uint32_t n, zh_decimator **out) { ZH_GUARD(ctx);
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    zh_decimator *m = new (std::nothrow) zh_decimator();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0; m->words = 2;
-    int rc = dev_alloc(&m->cnt[0], (size_t)2 * n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], (size_t)2 * n);
-    if (!rc && n) {                                                                // init() :14-19: dval 0, dcount 1
-        std::vector<float> init((size_t)2 * n, 0.0f);
-        for (uint32_t v = 0; v < n; v++) init[(size_t)n + v] = 1.0f;
-        rc = upload_field(ctx, m->dval(0), init);
-        if (!rc) rc = upload_field(ctx, m->dval(1), init);
-    }
-    if (rc) { (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); delete m; return rc; }
-    zh_flipper_register(m);
-    *out = m;
-    return ZH_OK;
+    const zh_decimator_state init{0.0f, 1.0f};                                     // init() :14-19: dval 0, dcount 1
+    return flip_create<DecimatorLayout>(ctx, n, out, &init);
 }
-int zh_decimator_destroy(zh_decimator *m) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    zh_flipper_unregister(m);
-    (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]);
-    delete m;
-    return ZH_OK;
-}
-int zh_decimator_get_state(zh_decimator *m, zh_decimator_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    std::vector<float> w;
-    int rc = download_field(m->ctx, w, m->dval(m->cur), (size_t)2 * m->n);
-    if (rc) return rc;
-    for (uint32_t v = 0; v < m->n; v++) host[v] = zh_decimator_state{w[v], w[(size_t)m->n + v]};
-    return ZH_OK;
-}
-int zh_decimator_set_state(zh_decimator *m, const zh_decimator_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    std::vector<float> w((size_t)2 * m->n);
-    for (uint32_t v = 0; v < m->n; v++) { w[v] = host[v].dval; w[(size_t)m->n + v] = host[v].dcount; }
-    return upload_field(m->ctx, m->dval(m->cur), w);
-}
+int zh_decimator_destroy(zh_decimator *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_decimator_get_state(zh_decimator *m, zh_decimator_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<DecimatorLayout>(m, host); }
+int zh_decimator_set_state(zh_decimator *m, const zh_decimator_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<DecimatorLayout>(m, host); }
 int zh_decimator_paint(zh_decimator *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                        zh_bool note_id_changed, const zh_decimator_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps; (void)note_id_changed;                                            // Decimator.zig:29-30
@@ -2114,51 +2000,10 @@ int zh_decimator_paint(zh_decimator *m, uint32_t start, uint32_t end, const zh_b
 }
 
 // ------------------------------------------------------------------ Curve
-int zh_curve_module_create(zh_ctx *ctx, uint32_t n, zh_curve_module **out) { ZH_GUARD(ctx);
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    zh_curve_module *m = new (std::nothrow) zh_curve_module();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0; m->words = 4;
-    int rc = dev_alloc(&m->cnt[0], (size_t)4 * n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], (size_t)4 * n);
-    for (int b = 0; b < 2 && !rc && n; b++) rc = (int)hipMemsetAsync(m->cnt[b], 0, (size_t)4 * n * 4, ctx->stream);   // init() :46-54
-    if (rc) { (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); delete m; return rc; }
-    zh_flipper_register(m);
-    *out = m;
-    return ZH_OK;
-}
-int zh_curve_module_destroy(zh_curve_module *m) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    zh_flipper_unregister(m);
-    (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]);
-    delete m;
-    return ZH_OK;
-}
-int zh_curve_module_get_state(zh_curve_module *m, zh_curve_module_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    std::vector<uint32_t> w;
-    int rc = download_field(m->ctx, w, m->cnt[m->cur], (size_t)4 * m->n);
-    if (rc) return rc;
-    const size_t n = m->n;
-    for (uint32_t v = 0; v < m->n; v++) {
-        zh_curve_module_state e;
-        memcpy(&e.t, &w[v], 4);
-        e.current_song_note = w[n + v]; e.current_song_note_offset = (int32_t)w[2 * n + v]; e.next_song_note = w[3 * n + v];
-        host[v] = e;
-    }
-    return ZH_OK;
-}
-int zh_curve_module_set_state(zh_curve_module *m, const zh_curve_module_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w(4 * n);
-    for (uint32_t v = 0; v < m->n; v++) {
-        memcpy(&w[v], &host[v].t, 4);
-        w[n + v] = host[v].current_song_note; w[2 * n + v] = (uint32_t)host[v].current_song_note_offset; w[3 * n + v] = host[v].next_song_note;
-    }
-    return upload_field(m->ctx, m->cnt[m->cur], w);
-}
+int zh_curve_module_create(zh_ctx *ctx, uint32_t n, zh_curve_module **out) { ZH_GUARD(ctx); return flip_create<CurveModuleLayout>(ctx, n, out); }   // init() :46-54
+int zh_curve_module_destroy(zh_curve_module *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_curve_module_get_state(zh_curve_module *m, zh_curve_module_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<CurveModuleLayout>(m, host); }
+int zh_curve_module_set_state(zh_curve_module *m, const zh_curve_module_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<CurveModuleLayout>(m, host); }
 int zh_curve_module_paint(zh_curve_module *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                           zh_bool note_id_changed, const zh_curve_module_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;
@@ -2186,16 +2031,10 @@ int zh_curve_module_paint(zh_curve_module *m, uint32_t start, uint32_t end, cons
 }
 
 // ------------------------------------------------------------------ Cycle
-int zh_cycle_create(zh_ctx *ctx, uint32_t n, zh_cycle **out) { ZH_GUARD(ctx); return flip1_create(ctx, n, out); }   // init() :16-20: t = 0
-int zh_cycle_destroy(zh_cycle *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip1_destroy(m); }
-int zh_cycle_get_state(zh_cycle *m, zh_cycle_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_download(m->ctx, host, m->t(), (size_t)m->n * 4);
-}
-int zh_cycle_set_state(zh_cycle *m, const zh_cycle_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_upload(m->ctx, m->t(), host, (size_t)m->n * 4);
-}
+int zh_cycle_create(zh_ctx *ctx, uint32_t n, zh_cycle **out) { ZH_GUARD(ctx); return flip_create<CycleLayout>(ctx, n, out); }   // init() :16-20: t = 0
+int zh_cycle_destroy(zh_cycle *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_cycle_get_state(zh_cycle *m, zh_cycle_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<CycleLayout>(m, host); }
+int zh_cycle_set_state(zh_cycle *m, const zh_cycle_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<CycleLayout>(m, host); }
 int zh_cycle_paint(zh_cycle *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                    zh_bool note_id_changed, const zh_cycle_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps; (void)note_id_changed;                                            // Cycle.zig:30-31
@@ -2228,43 +2067,10 @@ int zh_cycle_paint(zh_cycle *m, uint32_t start, uint32_t end, const zh_buf *outp
 }
 
 // ------------------------------------------------------------------ Portamento
-int zh_portamento_create(zh_ctx *ctx, uint32_t n, zh_portamento **out) { ZH_GUARD(ctx);
-    if (!ctx || !out) return ZH_ERR_INVALID;
-    zh_portamento *m = new (std::nothrow) zh_portamento();
-    if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0; m->words = 3;
-    int rc = dev_alloc(&m->cnt[0], (size_t)3 * n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], (size_t)3 * n);
-    for (int b = 0; b < 2 && !rc && n; b++) rc = (int)hipMemsetAsync(m->cnt[b], 0, (size_t)3 * n * 4, ctx->stream);   // Painter.init(), painter.zig:38-44
-    if (rc) { (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]); delete m; return rc; }
-    zh_flipper_register(m);
-    *out = m;
-    return ZH_OK;
-}
-int zh_portamento_destroy(zh_portamento *m) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m) return ZH_ERR_INVALID;
-    (void)hipStreamSynchronize(m->ctx->stream);
-    zh_flipper_unregister(m);
-    (void)hipFree(m->cnt[0]); (void)hipFree(m->cnt[1]);
-    delete m;
-    return ZH_OK;
-}
-int zh_portamento_get_state(zh_portamento *m, zh_portamento_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    std::vector<float> w;
-    int rc = download_field(m->ctx, w, m->f(m->cur, 0), (size_t)3 * m->n);
-    if (rc) return rc;
-    const size_t n = m->n;
-    for (uint32_t v = 0; v < m->n; v++) host[v] = zh_portamento_state{w[v], w[n + v], w[2 * n + v]};
-    return ZH_OK;
-}
-int zh_portamento_set_state(zh_portamento *m, const zh_portamento_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<float> w(3 * n);
-    for (uint32_t v = 0; v < m->n; v++) { w[v] = host[v].t; w[n + v] = host[v].last_value; w[2 * n + v] = host[v].start; }
-    return upload_field(m->ctx, m->f(m->cur, 0), w);
-}
+int zh_portamento_create(zh_ctx *ctx, uint32_t n, zh_portamento **out) { ZH_GUARD(ctx); return flip_create<PortamentoLayout>(ctx, n, out); }   // Painter.init(), painter.zig:38-44
+int zh_portamento_destroy(zh_portamento *m) { ZH_GUARD(m ? m->ctx : nullptr); return flip_destroy(m); }
+int zh_portamento_get_state(zh_portamento *m, zh_portamento_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<PortamentoLayout>(m, host); }
+int zh_portamento_set_state(zh_portamento *m, const zh_portamento_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<PortamentoLayout>(m, host); }
 int zh_portamento_paint(zh_portamento *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                         zh_bool note_id_changed, const zh_portamento_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps;

@@ -17,6 +17,7 @@
 #include "seq.hip.h"
 #include "voices.hip.h"
 #include "span_walk.hip.h"
+#include "module_state.hip.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <vector>
@@ -607,16 +608,12 @@ template <class M> static int osc_common_check(M *m, uint32_t start, uint32_t en
 }
 
 template <class M> static int osc_create_common(zh_ctx *ctx, M *m, uint32_t n, int kw) {
-    m->ctx = ctx; m->n = n; m->cur = 0; m->cnt[0] = m->cnt[1] = nullptr; m->id = 0;
     m->tab.words = nullptr; m->tab.valid = false; m->tab.pinned = false;
-    int rc = dev_alloc(&m->cnt[0], n);
-    if (!rc) rc = dev_alloc(&m->cnt[1], n);
+    int rc = flip_alloc(ctx, m, n, 1);                                  // init(): cnt = 0 (PulseOsc.zig:38-42, TriSawOsc.zig:39-44)
     if (!rc) rc = dev_alloc(&m->tab.words, (size_t)(kw + 1) * n);
-    if (!rc && n) rc = (int)hipMemsetAsync(m->cnt[0], 0, (size_t)n * 4, ctx->stream);   // init(): cnt = 0 (PulseOsc.zig:38-42, TriSawOsc.zig:39-44)
-    if (!rc && n) rc = (int)hipMemsetAsync(m->cnt[1], 0, (size_t)n * 4, ctx->stream);
     return rc;
 }
-template <class M> static void osc_free_common(M *m) { hipFree(m->cnt[0]); hipFree(m->cnt[1]); hipFree(m->tab.words); }
+template <class M> static void osc_free_common(M *m) { flip_free(m); hipFree(m->tab.words); }
 
 extern "C" {
 
@@ -641,14 +638,8 @@ int zh_pulseosc_destroy(zh_pulseosc *m) { ZH_GUARD(m ? m->ctx : nullptr);
     delete m;
     return ZH_OK;
 }
-int zh_pulseosc_get_state(zh_pulseosc *m, zh_pulseosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_download(m->ctx, host, m->cnt[m->cur], (size_t)m->n * 4);
-}
-int zh_pulseosc_set_state(zh_pulseosc *m, const zh_pulseosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr);
-    if (!m || !host) return ZH_ERR_INVALID;
-    return zh_upload(m->ctx, m->cnt[m->cur], host, (size_t)m->n * 4);
-}
+int zh_pulseosc_get_state(zh_pulseosc *m, zh_pulseosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_get_state<PulseOscLayout>(m, host); }
+int zh_pulseosc_set_state(zh_pulseosc *m, const zh_pulseosc_state *host) { ZH_GUARD(m ? m->ctx : nullptr); return flip_set_state<PulseOscLayout>(m, host); }
 static int pulseosc_paint_n(zh_pulseosc *m, uint32_t start, uint32_t end, const zh_buf *outputs, uint32_t nb,
                             const zh_pulseosc_params *p, uint32_t flags) {
     if (!p) return ZH_ERR_INVALID;

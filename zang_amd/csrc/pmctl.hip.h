@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 // ---- the state's layout ------------------------------------------------------------------------------------------------
 // words per voice, [word][voice], in the order of the struct
@@ -18,23 +19,17 @@ enum { PC_RATIO_T = 0, PC_RATIO_LAST, PC_RATIO_START, PC_MULT_T, PC_MULT_LAST, P
        PC_ENV_STATE, PC_ENV_T, PC_ENV_LAST, PC_ENV_START, kPmctlState };
 
 inline void pc_pack(const zh_pmctl_state &s, uint32_t *w, size_t n, size_t v) {
-    w[(size_t)PC_RATIO_T * n + v] = zh_f32_bits(s.ratio.t); w[(size_t)PC_RATIO_LAST * n + v] = zh_f32_bits(s.ratio.last_value);
-    w[(size_t)PC_RATIO_START * n + v] = zh_f32_bits(s.ratio.start);
-    w[(size_t)PC_MULT_T * n + v] = zh_f32_bits(s.multiplier.t); w[(size_t)PC_MULT_LAST * n + v] = zh_f32_bits(s.multiplier.last_value);
-    w[(size_t)PC_MULT_START * n + v] = zh_f32_bits(s.multiplier.start);
+    porta_pack(s.ratio, w + (size_t)PC_RATIO_T * n + v, n);
+    porta_pack(s.multiplier, w + (size_t)PC_MULT_T * n + v, n);
     w[(size_t)PC_CARRIER_T * n + v] = zh_f32_bits(s.carrier.t); w[(size_t)PC_MODULATOR_T * n + v] = zh_f32_bits(s.modulator.t);
-    w[(size_t)PC_ENV_STATE * n + v] = s.env.state; w[(size_t)PC_ENV_T * n + v] = zh_f32_bits(s.env.t);
-    w[(size_t)PC_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)PC_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    env_pack(s.env, w + (size_t)PC_ENV_STATE * n + v, n);
 }
 inline void pc_unpack(zh_pmctl_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
-    s.ratio.t = zh_bits_f32(w[(size_t)PC_RATIO_T * n + v]); s.ratio.last_value = zh_bits_f32(w[(size_t)PC_RATIO_LAST * n + v]);
-    s.ratio.start = zh_bits_f32(w[(size_t)PC_RATIO_START * n + v]);
-    s.multiplier.t = zh_bits_f32(w[(size_t)PC_MULT_T * n + v]); s.multiplier.last_value = zh_bits_f32(w[(size_t)PC_MULT_LAST * n + v]);
-    s.multiplier.start = zh_bits_f32(w[(size_t)PC_MULT_START * n + v]);
+    s.ratio = porta_unpack(w + (size_t)PC_RATIO_T * n + v, n);
+    s.multiplier = porta_unpack(w + (size_t)PC_MULT_T * n + v, n);
     s.carrier.t = zh_bits_f32(w[(size_t)PC_CARRIER_T * n + v]); s.modulator.t = zh_bits_f32(w[(size_t)PC_MODULATOR_T * n + v]);
-    s.env.state = w[(size_t)PC_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)PC_ENV_T * n + v]);
-    s.env.last_value = zh_bits_f32(w[(size_t)PC_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)PC_ENV_START * n + v]);
+    s.env = env_unpack(w + (size_t)PC_ENV_STATE * n + v, n);
 }
 using PmctlLayout = VoiceLayout<zh_pmctl_state, kPmctlState, pc_pack, pc_unpack>;
 

@@ -7,19 +7,18 @@
 #include <stddef.h>
 #include <string.h>
 #include "span_voice.hip.h"
+#include "module_state.hip.h"
 
 enum { SE_OSC_CNT = 0, SE_OSC_T, SE_ENV_STATE, SE_ENV_T, SE_ENV_LAST, SE_ENV_START, kSawEnvState };   // words per voice, [word][voice]
 
 inline void se_pack(const zh_saw_env_state &s, uint32_t *w, size_t n, size_t v) {
     w[(size_t)SE_OSC_CNT * n + v] = s.osc.cnt; w[(size_t)SE_OSC_T * n + v] = zh_f32_bits(s.osc.t);
-    w[(size_t)SE_ENV_STATE * n + v] = s.env.state; w[(size_t)SE_ENV_T * n + v] = zh_f32_bits(s.env.t);
-    w[(size_t)SE_ENV_LAST * n + v] = zh_f32_bits(s.env.last_value); w[(size_t)SE_ENV_START * n + v] = zh_f32_bits(s.env.start);
+    env_pack(s.env, w + (size_t)SE_ENV_STATE * n + v, n);
 }
 inline void se_unpack(zh_saw_env_state &s, const uint32_t *w, size_t n, size_t v) {
     memset(&s, 0, sizeof(s));
     s.osc.cnt = w[(size_t)SE_OSC_CNT * n + v]; s.osc.t = zh_bits_f32(w[(size_t)SE_OSC_T * n + v]);
-    s.env.state = w[(size_t)SE_ENV_STATE * n + v]; s.env.t = zh_bits_f32(w[(size_t)SE_ENV_T * n + v]);
-    s.env.last_value = zh_bits_f32(w[(size_t)SE_ENV_LAST * n + v]); s.env.start = zh_bits_f32(w[(size_t)SE_ENV_START * n + v]);
+    s.env = env_unpack(w + (size_t)SE_ENV_STATE * n + v, n);
 }
 using SawEnvLayout = VoiceLayout<zh_saw_env_state, kSawEnvState, se_pack, se_unpack>;
 

@@ -1,33 +1,15 @@
 // span_voice.hip.h -- what the fused voices that paint one LANE per voice from a span table share (lead.hip, hard_square.hip,
-// saw_env.hip, detuned.hip; laser.hip takes the host side alone, curve_player.hip all but the kernel's body).  Three parts:
-//   the float <-> word pair of every state layout, as plain C++ (the stand-alone harnesses of tests/cpp include it);
-//   the device side (hipcc only): the frame loop over one or two columns, and ZH_SPAN_VOICE_KERNEL, the kernel on span_walk's
-//   segments under each voice's stable kernel name;
-//   the host side: the handle {ctx, n, state} with create / destroy / get_state / set_state over a Layout, the zf x o1 launch
-//   switch, and the two paint entry points.
+// saw_env.hip, detuned.hip; laser.hip takes the host side alone, curve_player.hip all but the kernel's body).  Two parts, both
+// hipcc only (what a state Layout is made of, the plain C++ the stand-alone harnesses of tests/cpp include, and the block-level
+// get / set: state_block.hip.h, which this header includes):
+//   the device side: the frame loop over one or two columns, and ZH_SPAN_VOICE_KERNEL, the kernel on span_walk's segments under
+//   each voice's stable kernel name;
+//   the host side: the handle {ctx, n, state} with create / destroy / get_state / set_state over a Layout (PortaLayout,
+//   VibratoLayout, HardSquareLayout, SawEnvLayout, DetunedLayout, LaserLayout, CurvePlayerLayout, ...), the zf x o1 launch switch,
+//   and the two paint entry points.
 // A voice's translation unit is then its handle type, one ZH_SPAN_VOICE_KERNEL line, patch_default and the extern "C" wrappers.
 #pragma once
-#include <stdint.h>
-#include <stddef.h>
-#include <string.h>
-#include "../../include/zang_hip.h"
-
-inline uint32_t zh_f32_bits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
-inline float zh_bits_f32(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
-
-// A Layout (PortaLayout, VibratoLayout, HardSquareLayout, SawEnvLayout, DetunedLayout, LaserLayout, CurvePlayerLayout) is what the host side reads of
-// a voice's state, plain C++ beside the voice's struct:
-//   State                                   the ABI struct of one voice
-//   kWords                                  words per voice; the device block is uint32_t[kWords][n]
-//   pack(s, w, n, v) / unpack(s, w, n, v)   voice v of n: struct -> rows and back
-// (tests/cpp/lead_state_host.cpp runs every one of them under ASan and UBSan.)
-template <class S, int WORDS, void (*PACK)(const S &, uint32_t *, size_t, size_t), void (*UNPACK)(S &, const uint32_t *, size_t, size_t)>
-struct VoiceLayout {
-    using State = S;
-    enum { kWords = WORDS };
-    static void pack(const State &s, uint32_t *w, size_t n, size_t v) { PACK(s, w, n, v); }
-    static void unpack(State &s, const uint32_t *w, size_t n, size_t v) { UNPACK(s, w, n, v); }
-};
+#include "state_block.hip.h"
 
 #if defined(__HIPCC__)
 #include "common.hip.h"
@@ -117,9 +99,8 @@ template <class M> static int voice_create(zh_ctx *ctx, uint32_t n, uint32_t wor
     if (!ctx || !out) return ZH_ERR_INVALID;
     M *m = new (std::nothrow) M();
     if (!m) return ZH_ERR_INVALID;
-    m->ctx = ctx; m->n = n; m->state = nullptr;
-    int rc = dev_alloc(&m->state, (size_t)words * n);
-    if (!rc && n) { hipError_t e = hipMemsetAsync(m->state, 0, (size_t)words * n * 4, ctx->stream); if (e != hipSuccess) rc = (int)e; }
+    m->ctx = ctx; m->n = n;
+    int rc = dev_alloc_zeroed(ctx, &m->state, (size_t)words * n);
     if (rc) { (void)hipFree(m->state); delete m; return rc; }
     *out = m;
     return ZH_OK;
@@ -132,20 +113,10 @@ template <class M> static int voice_destroy(M *m) {
     return ZH_OK;
 }
 template <class LY> static int voice_get_state(zh_voice *m, typename LY::State *host) {
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)LY::kWords * n);
-    int rc = zh_download(m->ctx, w.data(), m->state, w.size() * 4);
-    if (rc) return rc;
-    for (size_t v = 0; v < n; v++) LY::unpack(host[v], w.data(), n, v);
-    return ZH_OK;
+    return m && host ? block_get_state<LY>(m->ctx, m->state, m->n, host) : ZH_ERR_INVALID;
 }
 template <class LY> static int voice_set_state(zh_voice *m, const typename LY::State *host) {
-    if (!m || !host) return ZH_ERR_INVALID;
-    const size_t n = m->n;
-    std::vector<uint32_t> w((size_t)LY::kWords * n);
-    for (size_t v = 0; v < n; v++) LY::pack(host[v], w.data(), n, v);
-    return n ? zh_upload(m->ctx, m->state, w.data(), w.size() * 4) : ZH_OK;
+    return m && host ? block_set_state<LY>(m->ctx, m->state, m->n, host) : ZH_ERR_INVALID;
 }
 
 // The paints of a lane L that also names
