@@ -883,7 +883,11 @@ ZH_API int zh_script_module_paint_spans(zh_script_module *m, uint32_t span_start
  * (the form is exact only).  ZH_PAINT_PARAMS_UNCHANGED is ignored: the form neither reads nor stores the constants it lets a
  * PulseOsc / TriSawOsc paint reuse, and it counts as that module's previous paint -- the next flagged zh_<osc>_paint
  * recomputes its constants.  No voices: ZH_OK, nothing runs.  No host sync: capturable; under ZH_CAPTURE_COALESCE it records what was held
- * back first.  Module state follows the plain paints' bookkeeping, so span paints, plain paints and graph replays mix. */
+ * back first.  Module state follows the plain paints' bookkeeping, so span paints, plain paints and graph replays mix.
+ * The overlap rules at the top of this header hold for the span forms (zh_script_module_paint_spans too): a ZH_PAINT_ZERO_FIRST
+ * paint whose input or control image overlaps outputs[0] reads the zeros -- the library zeroes the span, then paints with
+ * ZH_PAINT_ADD -- and an image that IS outputs[0] is read in the reference's order (SineOsc and TriSawOsc read a frame's
+ * frequency after their own add to that frame, every other image is read before it). */
 enum { ZH_SINEOSC_SPAN_FREQ = 0,          /* f (a constant freq only) */
        ZH_SINEOSC_SPAN_PHASE,             /* f (a constant phase only) */
        ZH_SINEOSC_SPAN_FIELDS };
@@ -1084,7 +1088,7 @@ ZH_API int zh_laser_paint_spans(zh_laser *m, uint32_t span_start, uint32_t span_
  * and graph replays of one zh_detuned mix.  outputs[0] = the voice, outputs[1] = the frequency image (the reference's
  * oscilloscope sync); an outputs[1] whose ptr is NULL is not painted.
  * ZH_ERR_INVALID: what zh_laser_paint[_spans] refuses, an outputs[0] that is NULL or too small, an outputs[1] that is not NULL
- * and too small. */
+ * and too small or shares a float with outputs[0] (as zh_stereo_echoes_paint: column ranges of one allocation with one stride do not). */
 typedef struct zh_detuned zh_detuned;
 typedef struct zh_detuned_patch {          /* the reference's constants; uniform over a call */
     float warble_hz, warble_wide;          /* 4.0, 4.0       :146, :153 */
@@ -1138,7 +1142,7 @@ ZH_API int zh_detuned_paint_spans(zh_detuned *m, uint32_t span_start, uint32_t s
  * ZH_ERR_UNSUPPORTED; frames outside every sub-span touch nothing; a field without a span array takes its value from `params` (a
  * broadcast value or a per-voice device array).  zh_curve_player_paint is the same kernel over one sub-span per voice.  Neither
  * paint allocates or synchronises: both are capturable, and paints, span paints and graph replays of one zh_curve_player mix.
- * ZH_ERR_INVALID: what zh_laser_paint[_spans] refuses, an outputs[1] that is not NULL and too small. */
+ * ZH_ERR_INVALID: what zh_laser_paint[_spans] refuses, an outputs[1] that is not NULL and too small or shares a float with outputs[0] (as zh_stereo_echoes_paint: column ranges of one allocation with one stride do not). */
 typedef struct zh_curve_player zh_curve_player;
 typedef struct zh_curve_player_params {                                                                /* :36-39 */
     float sample_rate; uint32_t reserved;
@@ -1206,7 +1210,7 @@ ZH_API int zh_curve_player_paint_spans(zh_curve_player *m, uint32_t span_start, 
  * without a span array takes its value from `params` (a broadcast value or a per-voice device array).  Neither paint allocates
  * or synchronises: both are capturable, and paints, span paints and graph replays of one object mix.
  * ZH_ERR_INVALID: what zh_detuned_paint[_spans] refuses, an outputs[0] that is NULL or too small, an outputs[1] that is not NULL
- * and too small. */
+ * and too small or shares a float with outputs[0] (as zh_stereo_echoes_paint: column ranges of one allocation with one stride do not). */
 typedef struct zh_porta zh_porta;
 typedef struct zh_porta_patch {            /* the reference's constants; uniform over a call */
     uint32_t glide_curve;                  /* ZH_CURVE_*; ZH_CURVE_CUBED   :57 */
@@ -1264,7 +1268,8 @@ ZH_API int zh_vibrato_paint_spans(zh_vibrato *m, uint32_t span_start, uint32_t s
  * `+= freq`.  PulseOsc's per-paint prologue runs at every sub-span.  note_id_changed reaches no module of this voice.  Semantics of
  * the span paint: zh_<module>_paint_spans above; ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end) of BOTH outputs,
  * ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; no host sync: capturable.  ZH_ERR_INVALID: NULL arguments, end < start, an outputs[0]
- * that is NULL or too small, an outputs[1] that is not NULL and too small, what zh_<module>_paint_spans refuses. */
+ * that is NULL or too small, an outputs[1] that is not NULL and too small or shares a float with outputs[0] (as zh_stereo_echoes_paint: column ranges of one allocation with one stride do not), what
+ * zh_<module>_paint_spans refuses. */
 typedef struct zh_hard_square zh_hard_square;
 typedef struct zh_hard_square_params {                                                                 /* modules.zig:253-257 */
     float sample_rate; uint32_t reserved;
@@ -1494,7 +1499,8 @@ ZH_API int zh_span_merge_overflows(zh_span_merge *m, uint64_t *out);
  * ZH_PAINT_ZERO_FIRST, which the player uses, the two are identical.  Semantics of the span paint: zh_<module>_paint_spans above;
  * ZH_PAINT_ZERO_FIRST writes all of [span_start, span_end) of BOTH outputs, ZH_PAINT_TOLERANT is ZH_ERR_UNSUPPORTED; no host sync:
  * capturable.  ZH_ERR_INVALID: NULL arguments, end < start, an outputs[0] that is NULL or too small, an outputs[1] that is not
- * NULL and too small, what zh_<module>_paint_spans refuses. */
+ * NULL and too small or shares a float with outputs[0] (as zh_stereo_echoes_paint: column ranges of one allocation with one stride do not), what
+ * zh_<module>_paint_spans refuses. */
 typedef struct zh_dual zh_dual;
 typedef struct zh_dual_patch {             /* the reference's constants; uniform over a call */
     float attack, decay, release;          /* cubed durations 0.025, 0.1, 1.0        :132-134 */

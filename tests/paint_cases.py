@@ -58,6 +58,7 @@ GEOMETRIES = {
 class _Backing:
     def __init__(self, t):
         self.t, self.snap, self.window = t, None, None     # window = (row0, row1, col0, col1) a paint may write, or None
+        self.more = []                                     # further windows (Geometry.writable: a voice's second output column)
 
     def snapshot(self):
         self.snap = self.t.view(_torch().int32).clone()
@@ -89,6 +90,7 @@ class Geometry:
         self.arrays = []                # _Backing of every per-voice array
         self._shared = []               # shared_allocation: the backings, and which roles of each are handed out
         self._out = None                # shared_allocation: the one output view
+        self._last = {}                 # role -> the backing of the view handed out last
 
     # ---- images
     def _canary(self, shape):
@@ -134,8 +136,15 @@ class Geometry:
             view.fill_(float(fill))
         if role == "out":
             b.window = (GUARD_ROWS + self.span[0], GUARD_ROWS + self.span[1], off, off + self.V)
+            b.more = []
+        self._last[role] = b
         b.snapshot()
         return view
+
+    def writable(self, role):
+        """The view of `role` handed out last is an output too (a voice's second column, outputs[1]): its span rows may change."""
+        off, _ = self.layout(role)
+        self._last[role].more.append((GUARD_ROWS + self.span[0], GUARD_ROWS + self.span[1], off, off + self.V))
 
     def per_voice(self, array):
         """A contiguous 1-D device slice holding `array` (float32 or uint8 / bool) at the geometry's element offset from a
@@ -175,13 +184,12 @@ class Geometry:
             for k, b in enumerate(group):
                 now = b.t.view(torch.int32) if b.t.dtype == torch.float32 else b.t
                 diff = now != b.snap
-                if b.window is not None:
-                    r0, r1, c0, c1 = b.window
+                for r0, r1, c0, c1 in ([] if b.window is None else [b.window]) + b.more:
                     diff[r0:r1, c0:c1] = False
                 n = int(diff.sum())
                 if n:
                     first = [int(x) for x in torch.nonzero(diff)[0]]
-                    where = "outside view x span of an output" if b.window is not None else "in a tensor no paint may write"
+                    where = "outside view x span of an output" if b.window is not None or b.more else "in a tensor no paint may write"
                     raise AssertionError(f"{what} [{self.name}, {self.V} voices]: {n} elements changed {where} ({kind} {k}, "
                                          f"shape {tuple(b.t.shape)}, window {b.window}), first at {first}")
 

@@ -277,6 +277,10 @@ def test_refusals(ctx, kits):
     assert m._paint_spans(span, [out0[:50], out1], None, good, table(), abi.PAINT_ADD) == abi.ZH_ERR_INVALID        # outputs[0]: too few rows
     assert m._paint_spans(span, [out0, out1[:50]], None, good, table(), abi.PAINT_ADD) == abi.ZH_ERR_INVALID        # a small outputs[1]
     assert m._paint_spans(span, [out0, out1[:, :V - 1]], None, good, table(), abi.PAINT_ADD) == abi.ZH_ERR_INVALID  # too few voices
+    wide, marker = ctx.image(cc.ROWS, 2 * V, fill=0.5), ctx.last_form()    # outputs[1] shares a float with outputs[0]: refused, no launch
+    assert m._paint_spans(span, [out0, out0], None, good, table(), abi.PAINT_ADD) == abi.ZH_ERR_INVALID                  # the same image
+    assert m._paint_spans(span, [wide[:, :V], wide[:, V - 1:2 * V - 1]], None, good, table(), abi.PAINT_ADD) == abi.ZH_ERR_INVALID   # one column in common
+    assert ctx.last_form() == marker
     with pytest.raises(abi.ZangHipError):
         m.paint(span, [out0, out1[:50]], [], False, good)
     outs = (abi.Buf * 2)(as_buf(out0), as_buf(out1))

@@ -394,6 +394,10 @@ def test_refusals(ctx):
     assert m._paint_spans(span, [out[:50], sync], None, good, _table(m, tb), abi.PAINT_ADD) == abi.ZH_ERR_INVALID      # too few rows
     assert m._paint_spans(span, [out[:, :V - 1], sync], None, good, _table(m, tb), abi.PAINT_ADD) == abi.ZH_ERR_INVALID  # too few voices
     assert m._paint_spans(span, [out, sync[:50]], None, good, _table(m, tb), abi.PAINT_ADD) == abi.ZH_ERR_INVALID      # the second output too small
+    wide, marker = ctx.image(dc.ROWS, 2 * V, fill=0.5), ctx.last_form()    # outputs[1] shares a float with outputs[0]: refused, no launch
+    assert m._paint_spans(span, [out, out], None, good, _table(m, tb), abi.PAINT_ADD) == abi.ZH_ERR_INVALID                  # the same image
+    assert m._paint_spans(span, [wide[:, :V], wide[:, V - 1:2 * V - 1]], None, good, _table(m, tb), abi.PAINT_ADD) == abi.ZH_ERR_INVALID   # one column in common
+    assert ctx.last_form() == marker
     with pytest.raises(abi.ZangHipError):
         m.paint(span, [out[:50]], [], False, good)
     outs = (abi.Buf * 2)(as_buf(out), as_buf(sync))

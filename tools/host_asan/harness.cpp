@@ -102,6 +102,10 @@ static void paint(Ctx &cx, Mod &m, const Fixed *fx = nullptr) {
         p.attack.duration = f32c(0.004f); p.decay.duration = f32p(m.color); p.release.duration = f32c(0.03f); p.sustain_volume = f32c(0.6f); p.note_on = boolc(pick(2));
         rc = zh_envelope_paint((zh_envelope *)m.h, s, e, &out, nullptr, boolc(pick(2)), &p, flags); break; }
     case DECIM: { zh_decimator_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.input = image(cx, m.V, 12); p.fake_sample_rate = f32p(m.freq);   // (image 12: never an output)
+        if (!fx && !pick(4)) {   // an in-place span paint: the input IS the output, so ZERO_FIRST zeroes the span before the paint (any device address passes as a table array)
+            const zh_script_span_table t{1, 0, (const uint32_t *)m.freq, (const uint32_t *)m.color, (const uint32_t *)m.color, (const uint8_t *)m.freq};
+            p.input = out;
+            rc = zh_decimator_paint_spans((zh_decimator *)m.h, s, e, &out, nullptr, &p, nullptr, &t, ZH_PAINT_ZERO_FIRST); break; }
         rc = zh_decimator_paint((zh_decimator *)m.h, s, e, &out, nullptr, boolc(0), &p, flags); break; }
     case PMOSC: { zh_pmosc_params p; memset(&p, 0, sizeof p); p.sample_rate = 48000.0f; p.freq = f32p(m.freq); p.note_on = boolc(pick(2));
         rc = zh_pmosc_paint((zh_pmosc *)m.h, s, e, &out, nullptr, boolc(pick(2)), &p, flags); break; }

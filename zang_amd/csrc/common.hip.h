@@ -249,6 +249,15 @@ static inline bool bufs_alias(const zh_buf &a, const zh_buf &b) {
     const float *ae = a.ptr + (size_t)a.frames * a.stride, *be = b.ptr + (size_t)b.frames * b.stride;
     return a.ptr < be && b.ptr < ae;
 }
+// do two views of n voices share a float?  With equal strides the rows of one lie at a fixed column offset inside the rows of the
+// other, so column ranges of one allocation are told apart; views of different strides whose extents intersect count as overlapping.
+static inline bool views_overlap(const zh_buf &a, const zh_buf &b, uint32_t n) {
+    if (!bufs_alias(a, b)) return false;
+    if (a.stride != b.stride) return true;
+    const uintptr_t S = a.stride, pa = (uintptr_t)a.ptr / sizeof(float), pb = (uintptr_t)b.ptr / sizeof(float);
+    const uintptr_t d = pb >= pa ? (pb - pa) % S : (S - (pa - pb) % S) % S;
+    return d < n || d + n > S;
+}
 static inline bool cob_aliases(const zh_cob &c, const zh_buf &b) { return c.tag == ZH_COB_BUFFER && bufs_alias(c.buffer, b); }
 // ZH_PAINT_ZERO_FIRST is "zang.zero(span, out), then the paint": a paint that READS an image overlapping outputs[0] must read the
 // zeros.  The fused forms start the output from 0 without storing it first, so they would read the image's old contents: every entry

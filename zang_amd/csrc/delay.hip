@@ -1051,15 +1051,6 @@ int zh_stereo_echoes_set_state(zh_stereo_echoes *m, const float *rings0, const u
     if (!rc) rc = zh_upload(m->ctx, m->s.b, b.data(), (size_t)n * 4);
     return rc;
 }
-// do two views of n voices share a float?  With equal strides the rows of one lie at a fixed column offset inside the rows of the
-// other, so column ranges of one allocation are told apart; views of different strides whose extents intersect count as overlapping.
-static bool views_overlap(const zh_buf &a, const zh_buf &b, uint32_t n) {
-    if (!bufs_alias(a, b)) return false;
-    if (a.stride != b.stride) return true;
-    const uintptr_t S = a.stride, pa = (uintptr_t)a.ptr / sizeof(float), pb = (uintptr_t)b.ptr / sizeof(float);
-    const uintptr_t d = pb >= pa ? (pb - pa) % S : (S - (pa - pb) % S) % S;
-    return d < n || d + n > S;
-}
 int zh_stereo_echoes_paint(zh_stereo_echoes *m, uint32_t start, uint32_t end, const zh_buf *outputs, const zh_buf *temps,
                            zh_bool note_id_changed, const zh_stereo_echoes_params *p, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
     (void)temps; (void)note_id_changed;                               // the four temps of the reference stay in registers

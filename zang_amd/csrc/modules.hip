@@ -2160,7 +2160,8 @@ int zh_distortion_paint(zh_distortion *m, uint32_t start, uint32_t end, const zh
 
 // ---- SineOsc: freq / phase per sub-span where they are constants; cob images read at the absolute frame
 struct SineSpanArgs { uint32_t V; const float *t_in; float *t_out; float sample_rate; CobP freq, phase; const float *sf, *sp; };
-template <bool FB, bool PB> struct SineSpans {
+// SELF: the freq image IS the output image -- each frame's frequency is read after its own add (SineOscLane::frame)
+template <bool FB, bool PB, bool SELF = false> struct SineSpans {
     using Args = SineSpanArgs;
     static constexpr int NIN = (FB ? 1 : 0) + (PB ? 1 : 0);
     SineOscLane o;
@@ -2178,7 +2179,7 @@ template <bool FB, bool PB> struct SineSpans {
         ph = PB ? 0.0f : span_f(a.sp, kv, phase0);
     }
     template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
-        val = o.template frame<FB>(FB ? x[0] : 0.0f, PB ? x[NI - 1] : ph);
+        val = o.template frame<FB, 1, SELF>(FB ? x[0] : 0.0f, PB ? x[NI - 1] : ph);
         return true;
     }
     __device__ __forceinline__ void end(const Args &) { o.end(); }  // :40
@@ -2411,11 +2412,16 @@ int zh_sineosc_paint_spans(zh_sineosc *m, uint32_t start, uint32_t end, const zh
     if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, cob_aliases(p->freq, outputs[0]) || cob_aliases(p->phase, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const SineSpanArgs a{m->n, m->t(), reinterpret_cast<float *>(m->cnt[m->cur ^ 1]), p->sample_rate, mk_cob(p->freq), mk_cob(p->phase),
                          span_fa(sp, ZH_SINEOSC_SPAN_FREQ), span_fa(sp, ZH_SINEOSC_SPAN_PHASE)};
-    if (fb && pb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<true, true>);
+    // the frequency image IS the output image: each frame's frequency is read after its own add, as zh_sineosc_paint does
+    if (fb && p->freq.buffer.ptr == outputs[0].ptr && p->freq.buffer.stride == outputs[0].stride) {    // (zf is off: zh_zero_first_aliased)
+        if (pb) ZH_LAUNCH((k_sineosc_spans<false, SineSpans<true, true, true>>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_walk(table), mk_img(outputs[0]), start, end);
+        else ZH_LAUNCH((k_sineosc_spans<false, SineSpans<true, false, true>>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_walk(table), mk_img(outputs[0]), start, end);
+    } else if (fb && pb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<true, true>);
     else if (fb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<true, false>);
     else if (pb) ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<false, true>);
     else ZH_MODULE_SPANS_LAUNCH(k_sineosc_spans, SineSpans<false, false>);
@@ -2481,6 +2487,8 @@ int zh_filter_paint_spans(zh_filter *m, uint32_t start, uint32_t end, const zh_b
     if ((cb && span_has(sp, ZH_FILTER_SPAN_CUTOFF)) || (rb && span_has(sp, ZH_FILTER_SPAN_RES))) return ZH_ERR_INVALID;
     if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
     if (m->n == 0) return ZH_OK;
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]) || cob_aliases(p->cutoff, outputs[0]) ||
+                                    cob_aliases(p->res, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const FilterSpanArgs a{m->n, m->l, m->b, mk_cimg(p->input), p->type, mk_cob(p->cutoff), mk_cob(p->res),
@@ -2580,6 +2588,7 @@ int zh_decimator_paint_spans(zh_decimator *m, uint32_t start, uint32_t end, cons
     if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const int c = m->cur;
@@ -2598,6 +2607,7 @@ int zh_distortion_paint_spans(zh_distortion *m, uint32_t start, uint32_t end, co
     if (p->type > ZH_DISTORTION_CLIP || !buf_covers(p->input, m->n, end)) return ZH_ERR_INVALID;
     if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
     if (m->n == 0) return ZH_OK;
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, bufs_alias(p->input, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const DistSpanArgs a{m->n, mk_cimg(p->input), p->type, mk_f32(p->ingain), mk_f32(p->outgain), mk_f32(p->offset),

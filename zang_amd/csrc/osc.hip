@@ -833,7 +833,8 @@ ZH_MODULE_SPANS_KERNEL(k_pulseosc_spans)
 
 // TriSawOsc: the constant-frequency path's counter (double-buffered) and the controlled path's f32 phase (one buffer, updated
 // in place: each lane reads and writes its own voice's)
-template <bool FB> struct TriSawSpans {
+// SELF: the freq image IS the output image -- each frame's frequency is read after its own add (TriSawOscLane::frame_ctrl)
+template <bool FB, bool SELF = false> struct TriSawSpans {
     using Args = OscSpanArgs;
     static constexpr int NIN = FB ? 1 : 0;
     TriSawOscLane o;
@@ -853,7 +854,7 @@ template <bool FB> struct TriSawSpans {
         else o.begin_const(a.sample_rate, span_f(a.sf, kv, freq0), color);   // :77-99
     }
     template <int NI> __device__ __forceinline__ bool frame(const Args &, const float (&x)[NI], float &val) {
-        if (FB) { val = o.frame_ctrl(x[0]); return true; }
+        if (FB) { val = o.template frame_ctrl<SELF>(x[0]); return true; }
         return o.frame_const(val);
     }
     __device__ __forceinline__ void end(const Args &) { if (FB) o.end_ctrl(); }   // :155
@@ -884,6 +885,7 @@ int zh_pulseosc_paint_spans(zh_pulseosc *m, uint32_t start, uint32_t end, const 
     if (rc) return rc;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, cob_aliases(p->freq, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const OscSpanArgs a{m->n, m->cnt[m->cur], m->cnt[m->cur ^ 1], nullptr, p->sample_rate, mk_cob(p->freq), mk_f32(p->color),
@@ -904,11 +906,15 @@ int zh_trisawosc_paint_spans(zh_trisawosc *m, uint32_t start, uint32_t end, cons
     if (rc) return rc;
     if (m->n == 0) return ZH_OK;
     zh_flipper_used(m);
+    if ((rc = zh_zero_first_aliased(m->ctx, start, end, outputs[0], m->n, cob_aliases(p->freq, outputs[0]), flags))) return rc;
     const bool zf = flags & ZH_PAINT_ZERO_FIRST;
     hipStream_t st = m->ctx->stream;
     const OscSpanArgs a{m->n, m->cnt[m->cur], m->cnt[m->cur ^ 1], m->t, p->sample_rate, mk_cob(p->freq), mk_f32(p->color),
                         span_fa(sp, ZH_TRISAWOSC_SPAN_FREQ), span_fa(sp, ZH_TRISAWOSC_SPAN_COLOR)};
-    if (p->freq.tag == ZH_COB_BUFFER) ZH_MODULE_SPANS_LAUNCH(k_trisawosc_spans, TriSawSpans<true>);
+    // the frequency image IS the output image: each frame's frequency is read after its own add, as zh_trisawosc_paint does
+    if (p->freq.tag == ZH_COB_BUFFER && p->freq.buffer.ptr == outputs[0].ptr && p->freq.buffer.stride == outputs[0].stride)    // (zf is off: it aliases)
+        ZH_LAUNCH((k_trisawosc_spans<false, TriSawSpans<true, true>>), seq_grid(m->n), dim3(kSeqBlock), 0, st, a, mk_span_walk(table), mk_img(outputs[0]), start, end);
+    else if (p->freq.tag == ZH_COB_BUFFER) ZH_MODULE_SPANS_LAUNCH(k_trisawosc_spans, TriSawSpans<true>);
     else ZH_MODULE_SPANS_LAUNCH(k_trisawosc_spans, TriSawSpans<false>);
     m->tab.valid = false;                   // (as zh_pulseosc_paint_spans)
     zh_flipper_painted(m);

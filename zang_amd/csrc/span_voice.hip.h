@@ -129,7 +129,10 @@ template <class L>
 static int voice_args(zh_voice *m, uint32_t start, uint32_t end, const zh_buf *outputs, const typename L::Params *p, const zh_script_span_param *sp,
                       typename L::Args &a) {
     if (!m || !outputs || !p || end < start || !buf_covers(outputs[0], m->n, end)) return ZH_ERR_INVALID;
-    if constexpr (L::kOutputs > 1) { if (outputs[1].ptr && !buf_covers(outputs[1], m->n, end)) return ZH_ERR_INVALID; }
+    // (the two columns are painted in one pass, each frame of outputs[1] after that of outputs[0]: they may not share a float)
+    if constexpr (L::kOutputs > 1) {
+        if (outputs[1].ptr && (!buf_covers(outputs[1], m->n, end) || views_overlap(outputs[0], outputs[1], m->n))) return ZH_ERR_INVALID;
+    }
     a = L::args(*m, *p, sp);
     return ZH_OK;
 }
