@@ -1,73 +1,16 @@
 """The yardstick of the arpeggiator tests; holds no tests.  examples/example_arpeggiator.zig restated line by line in Python, from
 the Zig alone: MainModule's ImpulseQueue and Trigger over the held-key records (:147-167), Arpeggiator.paint's tick loop with its
 own ImpulseQueue and IdGenerator (:56-104) and the inner Trigger (:106-107), each sub-span painted by the oracle's
-zo_hard_square_paint plus zo_add_scalar_into (:108-115).  Impulses are stored in lists here, as the reference stores them.
-Where the reference is undefined: an impulse below the Trigger's position (its assert, trigger.zig:161) is taken at the position."""
+zo_hard_square_paint plus zo_add_scalar_into (:108-115).  ImpulseQueue, Trigger and the stage's table are tests/span_reference.py's:
+impulses are stored in lists, as the reference stores them, and where the reference is undefined, an impulse below the Trigger's
+position (its assert, trigger.zig:161) is taken at the position."""
 import ctypes as C
 
 import numpy as np
 
+from tests.span_reference import MAX_IMPULSES, ImpulseQueue, Trigger, same_table, table  # noqa: F401  (for the tests)
+
 f32 = np.float32
-MAX_IMPULSES = 32                                  # notes.zig:73
-
-
-class ImpulseQueue:
-    """notes.zig:72-128: push drops at 32 and on a frame below the last accepted one's; consume empties"""
-
-    def __init__(self):
-        self.items = []                            # (frame, note_id, params)
-
-    def push(self, frame, note_id, params):
-        if len(self.items) >= MAX_IMPULSES:        # :108-111
-            return
-        if self.items and frame < self.items[-1][0]:   # :112-118
-            return
-        self.items.append((frame, note_id, params))
-
-    def consume(self):
-        items, self.items = self.items, []
-        return items
-
-
-class Trigger:
-    """trigger.zig:26-198; `note` = (id, params) or None"""
-
-    def __init__(self):
-        self.note = None
-
-    def spans(self, start, end, impulses):
-        """the Trigger.next loop over counter(Span(start, end), impulses): -> [(s, e, params, note_id_changed)]"""
-        out, idx, pos = [], 0, start
-        while pos < end:                                                       # :81
-            span = None
-            if self.note is not None:                                          # carryOver :107-137
-                if idx < len(impulses):
-                    nf = impulses[idx][0]
-                    if nf > pos:
-                        span = (pos, min(end, nf), self.note)
-                else:
-                    span = (pos, end, self.note)
-            if span is None:                                                   # getNextNoteSpan :139-196
-                span = (pos, end, None)
-                while idx < len(impulses):
-                    frame, note_id, params = impulses[idx]
-                    if frame >= end:                                           # :144-150
-                        break
-                    if frame > pos:                                            # :152-159
-                        span = (pos, frame, None)
-                        break
-                    idx += 1                                                   # :163 (:161 asserts frame == pos; below: taken here)
-                    clipped = min(end, impulses[idx][0]) if idx < len(impulses) else end   # :167-171
-                    if clipped <= pos:                                         # :173-178
-                        continue
-                    span = (pos, clipped, (note_id, params))
-                    break
-            pos = span[1]                                                      # :88
-            if span[2] is not None:                                            # :90-100
-                changed = True if self.note is None else span[2][0] != self.note[0]
-                out.append((span[0], span[1], span[2][1], changed))
-                self.note = span[2]
-        return out
 
 
 def note_duration(sample_rate):
@@ -160,35 +103,6 @@ class Player:
         for s, e, held, _ in outer:
             inner += self.arp.paint(s, e, out_len, sample_rate, held)
         return outer, inner
-
-
-def table(players_spans, max_spans):
-    """the stage's table from each player's inner sub-spans: rows at max_spans and beyond are dropped and counted"""
-    N = len(players_spans)
-    tb = {"count": np.zeros(N, np.uint32), "start": np.zeros((max_spans, N), np.uint32), "end": np.zeros((max_spans, N), np.uint32),
-          "nic": np.zeros((max_spans, N), np.uint8), "freq": np.zeros((max_spans, N), f32), "note_on": np.zeros((max_spans, N), np.uint32)}
-    dropped = 0
-    for p, spans in enumerate(players_spans):
-        tb["count"][p] = min(len(spans), max_spans)
-        dropped += max(0, len(spans) - max_spans)
-        for k, (s, e, (freq, on), changed) in enumerate(spans[:max_spans]):
-            tb["start"][k, p], tb["end"][k, p], tb["nic"][k, p], tb["freq"][k, p], tb["note_on"][k, p] = s, e, changed, freq, on
-    return tb, dropped
-
-
-def same_table(got, ref):
-    """counts equal, and every row below a player's count equal on bits; -> None or what differs first"""
-    if not np.array_equal(got["count"], ref["count"]):
-        return ("count", np.argwhere(got["count"] != ref["count"])[:4].tolist())
-    K = ref["start"].shape[0]
-    live = np.arange(K)[:, None] < ref["count"][None, :]
-    for name in ("start", "end", "nic", "note_on", "freq"):
-        a, b = got[name][:K], ref[name]
-        if name == "freq":
-            a, b = a.view(np.uint32), b.view(np.uint32)
-        if not np.array_equal(a[live], b[live]):
-            return (name, np.argwhere((a != b) & live)[:4].tolist())
-    return None
 
 
 class HardSquareVoice:

@@ -1,14 +1,9 @@
-// detuned_state_host.cpp -- the detuned voice's state layout (zang_amd/csrc/detuned.hip.h ds_pack / ds_unpack: what
+// detuned_state_host.cpp -- the detuned voice's state layout (zang_amd/csrc/detuned.hip.h DetunedLayout over ds_pack / ds_unpack: what
 // zh_detuned_set_state and zh_detuned_get_state run) as a stand-alone program for AddressSanitizer + UBSan.  For n = 0, 1, 65
 // and 130 voices: structs -> rows in a heap block of EXACTLY the library's size (kDetunedState * n words) -> structs again, every
 // field compared on bits; and every word of every row is written exactly once, at [word][voice].
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "../../zang_amd/csrc/detuned.hip.h"
-
-static int fail(const char *what, int a = 0, int b = 0) { printf("%s (%d, %d)\nFAIL\n", what, a, b); return 1; }
+#include "state_harness.h"
 
 static zh_detuned_state make(uint32_t v) {
     zh_detuned_state s;
@@ -21,33 +16,15 @@ static zh_detuned_state make(uint32_t v) {
     return s;
 }
 
-static int run(size_t n) {
-    std::vector<zh_detuned_state> in(n), out(n);
-    for (size_t v = 0; v < n; v++) in[v] = make((uint32_t)v);
-    const size_t words = (size_t)kDetunedState * n;
-    uint32_t *w = new uint32_t[words];                                // exactly the library's size
-    for (size_t i = 0; i < words; i++) w[i] = 0xDEADBEEFu;
-    for (size_t v = 0; v < n; v++) ds_pack(in[v], w, n, v);
-    for (size_t i = 0; i < words; i++)
-        if (w[i] == 0xDEADBEEFu) { delete[] w; return fail("a word not written", (int)(i / (n ? n : 1)), (int)(i % (n ? n : 1))); }
-    // [word][voice]: the scalar rows hold voice v's value at column v
-    for (size_t v = 0; v < n; v++) {
-        if (w[(size_t)DS_OSC_CNT * n + v] != in[v].osc.cnt || w[(size_t)DS_ENV_STATE * n + v] != in[v].env.state ||
-            w[(size_t)DS_RNG * n + v] != (uint32_t)in[v].noise.r[0] || w[(size_t)(DS_RNG + 7) * n + v] != (uint32_t)(in[v].noise.r[3] >> 32) ||
-            w[(size_t)DS_MF_B * n + v] != 0x80000000u) { delete[] w; return fail("row layout", (int)v); }
-    }
-    for (size_t v = 0; v < n; v++) ds_unpack(out[v], w, n, v);
-    delete[] w;
-    for (size_t v = 0; v < n; v++)
-        if (memcmp(&in[v], &out[v], sizeof(zh_detuned_state)) != 0) return fail("round trip", (int)v);
-    return 0;
-}
-
 int main() {
     static_assert(kDetunedState == 18, "18 words per voice");
     static_assert(sizeof(zh_detuned_state) == 104, "zh_detuned_state");
     for (size_t n : {(size_t)0, (size_t)1, (size_t)65, (size_t)130})
-        if (run(n)) return 1;
+        if (run<DetunedLayout>(n, make, [](const zh_detuned_state &s, const uint32_t *w, size_t n_, size_t v) {   // the scalar rows
+                return w[(size_t)DS_OSC_CNT * n_ + v] == s.osc.cnt && w[(size_t)DS_ENV_STATE * n_ + v] == s.env.state &&
+                       w[(size_t)DS_RNG * n_ + v] == (uint32_t)s.noise.r[0] && w[(size_t)(DS_RNG + 7) * n_ + v] == (uint32_t)(s.noise.r[3] >> 32) &&
+                       w[(size_t)DS_MF_B * n_ + v] == 0x80000000u;
+            })) return 1;
     // the taps are not part of the voice: packed from anything, they come back as zeros
     zh_detuned_state s = make(3), back;
     s.noise.b[2] = 7.0f; s.noise.reserved = 9;

@@ -3,13 +3,8 @@
 // + UBSan: the harness of lead_state_host.cpp, which runs the other six layouts, over the seventh.  For n = 0, 1, 65 and 130
 // voices: structs -> rows in a heap block of EXACTLY the library's size (kWords * n words) -> structs again, every field compared
 // on bits; and every word of every row is written exactly once, at [word][voice].
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "../../zang_amd/csrc/dual.hip.h"
-
-static int fail(const char *what, int a = 0, int b = 0) { printf("%s (%d, %d)\nFAIL\n", what, a, b); return 1; }
+#include "state_harness.h"
 
 static zh_dual_state make_dual(uint32_t v) {
     zh_dual_state s;
@@ -17,26 +12,6 @@ static zh_dual_state make_dual(uint32_t v) {
     s.osc.cnt = 0xFFFFFFFFu - v; s.osc.t = zh_bits_f32(0x80000000u);
     s.env.state = v % 5; s.env.t = 1.0f / (float)(v + 1); s.env.last_value = zh_bits_f32(0x7FC00001u + v); s.env.start = zh_bits_f32(0x00000001u + v);
     return s;
-}
-
-template <class LY, class Make, class Rows>
-static int run(size_t n, Make make, Rows rows) {
-    using State = typename LY::State;
-    std::vector<State> in(n), out(n);
-    for (size_t v = 0; v < n; v++) in[v] = make((uint32_t)v);
-    const size_t words = (size_t)LY::kWords * n;
-    uint32_t *w = new uint32_t[words];                                // exactly the library's size
-    for (size_t i = 0; i < words; i++) w[i] = 0xDEADBEEFu;
-    for (size_t v = 0; v < n; v++) LY::pack(in[v], w, n, v);
-    for (size_t i = 0; i < words; i++)
-        if (w[i] == 0xDEADBEEFu) { delete[] w; return fail("a word not written", (int)(i / (n ? n : 1)), (int)(i % (n ? n : 1))); }
-    for (size_t v = 0; v < n; v++)                                    // [word][voice]: the rows hold voice v's value at column v
-        if (!rows(in[v], w, n, v)) { delete[] w; return fail("row layout", (int)v); }
-    for (size_t v = 0; v < n; v++) LY::unpack(out[v], w, n, v);
-    delete[] w;
-    for (size_t v = 0; v < n; v++)
-        if (memcmp(&in[v], &out[v], sizeof(State)) != 0) return fail("round trip", (int)v);
-    return 0;
 }
 
 int main() {

@@ -3,17 +3,12 @@
 // zh_<voice>_set_state and zh_<voice>_get_state run) as a stand-alone program for AddressSanitizer + UBSan.  For n = 0, 1, 65 and
 // 130 voices: structs -> rows in a heap block of EXACTLY the library's size (kWords * n words) -> structs again, every field
 // compared on bits; and every word of every row is written exactly once, at [word][voice].
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "../../zang_amd/csrc/lead.hip.h"
 #include "../../zang_amd/csrc/hard_square.hip.h"
 #include "../../zang_amd/csrc/saw_env.hip.h"
 #include "../../zang_amd/csrc/detuned.hip.h"
 #include "../../zang_amd/csrc/laser.hip.h"
-
-static int fail(const char *what, int a = 0, int b = 0) { printf("%s (%d, %d)\nFAIL\n", what, a, b); return 1; }
+#include "state_harness.h"
 
 static zh_porta_state make_porta(uint32_t v) {
     zh_porta_state s;
@@ -64,26 +59,6 @@ static zh_laser_state make_laser(uint32_t v) {
     s.modulator_curve = make_curve(v, 1); s.modulator.t = zh_bits_f32(0x80000000u);
     s.volume_curve = make_curve(v, 2);
     return s;
-}
-
-template <class LY, class Make, class Rows>
-static int run(size_t n, Make make, Rows rows) {
-    using State = typename LY::State;
-    std::vector<State> in(n), out(n);
-    for (size_t v = 0; v < n; v++) in[v] = make((uint32_t)v);
-    const size_t words = (size_t)LY::kWords * n;
-    uint32_t *w = new uint32_t[words];                                // exactly the library's size
-    for (size_t i = 0; i < words; i++) w[i] = 0xDEADBEEFu;
-    for (size_t v = 0; v < n; v++) LY::pack(in[v], w, n, v);
-    for (size_t i = 0; i < words; i++)
-        if (w[i] == 0xDEADBEEFu) { delete[] w; return fail("a word not written", (int)(i / (n ? n : 1)), (int)(i % (n ? n : 1))); }
-    for (size_t v = 0; v < n; v++)                                    // [word][voice]: the rows hold voice v's value at column v
-        if (!rows(in[v], w, n, v)) { delete[] w; return fail("row layout", (int)v); }
-    for (size_t v = 0; v < n; v++) LY::unpack(out[v], w, n, v);
-    delete[] w;
-    for (size_t v = 0; v < n; v++)
-        if (memcmp(&in[v], &out[v], sizeof(State)) != 0) return fail("round trip", (int)v);
-    return 0;
 }
 
 int main() {

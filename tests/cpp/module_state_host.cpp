@@ -2,31 +2,15 @@
 // state_block.hip.h flip_get_state / flip_set_state / block_get_state / block_set_state over SineOscLayout, SamplerLayout,
 // CycleLayout, PulseOscLayout, EnvelopeLayout, PortamentoLayout, DecimatorLayout, CurveModuleLayout, PmoscLayout and FmLayout: what
 // zh_<module>_set_state and zh_<module>_get_state run) as a stand-alone program for AddressSanitizer + UBSan: the harness of
-// lead_state_host.cpp over the older half of the library.  For n = 0, 1, 65 and 130 voices: hostile structs -> rows in a heap
+// lead_state_host.cpp (state_harness.h, the read-back structs prefilled with 0xA5) over the older half of the library.  For n = 0, 1, 65 and 130 voices: hostile structs -> rows in a heap
 // block of EXACTLY the library's size (kWords * n words) -> structs again, compared on bits; every word of every row is written;
 // and named rows hold voice v's value at column v.  The rows are named here by what the KERNELS read, not by the Layout under
 // test: FMS_* (fm.hip.h FMOpLane), PM_* (composite.hip zh_pmosc::view), and for the modules of modules.hip / osc.hip, whose
 // kernels take `block + k * n` as their k-th pointer (zh_envelope::f, zh_decimator::dcount, zh_portamento::f, k_curve), k itself.
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "../../zang_amd/csrc/module_state.hip.h"
 #include "../../zang_amd/csrc/fm.hip.h"
+#include "state_harness.h"
 
-static int fail(const char *what, int a = 0, int b = 0) { printf("%s (%d, %d)\nFAIL\n", what, a, b); return 1; }
-
-// bit patterns a float field must carry untouched: NaN payloads (quiet and signalling), -0.0, denormals, all ones
-static float hostile(uint32_t v, uint32_t k) {
-    switch ((v + k) % 6) {
-    case 0: return zh_bits_f32(0x7FC00001u + v);
-    case 1: return zh_bits_f32(0x80000000u);
-    case 2: return zh_bits_f32(0x00000001u + v);
-    case 3: return zh_bits_f32(0xFFFFFFFFu);
-    case 4: return zh_bits_f32(0x7F800001u + 7 * v);
-    default: return zh_bits_f32(0x807FFFFFu - v);
-    }
-}
 static zh_envelope_state make_env(uint32_t v, uint32_t k = 0) { return zh_envelope_state{0xFFFFFFFFu - v - k, hostile(v, k), hostile(v, k + 1), hostile(v, k + 2)}; }
 static zh_sineosc_state make_sine(uint32_t v) { return zh_sineosc_state{hostile(v, 0)}; }
 static zh_sampler_state make_sampler(uint32_t v) { return zh_sampler_state{hostile(v, 1)}; }
@@ -52,30 +36,6 @@ static zh_fm_state make_fm(uint32_t v) {                              // `reserv
     return s;
 }
 
-template <class LY, class Make, class Rows>
-static int run(size_t n, Make make, Rows rows) {
-    using State = typename LY::State;
-    std::vector<State> in(n), out(n);
-    for (size_t v = 0; v < n; v++) in[v] = make((uint32_t)v);
-    const size_t words = (size_t)LY::kWords * n;
-    uint32_t *w = new uint32_t[words];                                // exactly the library's size
-    std::vector<bool> marked(words, false);                           // (a hostile value may itself be the marker: count only words that stay so under two markers)
-    for (uint32_t marker : {0xDEADBEEFu, 0x21524110u}) {
-        for (size_t i = 0; i < words; i++) w[i] = marker;
-        for (size_t v = 0; v < n; v++) LY::pack(in[v], w, n, v);
-        for (size_t i = 0; i < words; i++) {
-            if (marker == 0xDEADBEEFu) marked[i] = w[i] == marker;
-            else if (marked[i] && w[i] == marker) { delete[] w; return fail("a word not written", (int)(i / n), (int)(i % n)); }
-        }
-    }
-    for (size_t v = 0; v < n; v++)                                    // [word][voice]: the rows hold voice v's value at column v
-        if (!rows(in[v], w, n, v)) { delete[] w; return fail("row layout", (int)v); }
-    for (size_t v = 0; v < n; v++) { memset(&out[v], 0xA5, sizeof(State)); LY::unpack(out[v], w, n, v); }
-    delete[] w;
-    for (size_t v = 0; v < n; v++)
-        if (memcmp(&in[v], &out[v], sizeof(State)) != 0) return fail("round trip", (int)v);
-    return 0;
-}
 static bool env_rows(const zh_envelope_state &e, const uint32_t *s, size_t n) {      // s = the voice's word in the envelope's first row
     return s[0] == e.state && s[n] == zh_f32_bits(e.t) && s[2 * n] == zh_f32_bits(e.last_value) && s[3 * n] == zh_f32_bits(e.start);
 }
@@ -93,25 +53,25 @@ int main() {
     static_assert(PmoscLayout::kWords == 6 && sizeof(zh_pmosc_state) == 24, "6 words per PMOsc voice");
     static_assert(FmLayout::kWords == 14 && kFmState == 14 && sizeof(zh_fm_state) == 64, "14 words per FM voice (16 in the struct: `reserved` twice)");
     for (size_t n : {(size_t)0, (size_t)1, (size_t)65, (size_t)130}) {
-        if (run<SineOscLayout>(n, make_sine, [](const zh_sineosc_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); })) return 1;
-        if (run<SamplerLayout>(n, make_sampler, [](const zh_sampler_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); })) return 1;
-        if (run<CycleLayout>(n, make_cycle, [](const zh_cycle_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); })) return 1;
-        if (run<PulseOscLayout>(n, make_pulse, [](const zh_pulseosc_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == s.cnt; })) return 1;
-        if (run<EnvelopeLayout>(n, make_envelope, [](const zh_envelope_state &s, const uint32_t *w, size_t n_, size_t v) { return env_rows(s, w + v, n_); })) return 1;
+        if (run<SineOscLayout>(n, make_sine, [](const zh_sineosc_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); }, true)) return 1;
+        if (run<SamplerLayout>(n, make_sampler, [](const zh_sampler_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); }, true)) return 1;
+        if (run<CycleLayout>(n, make_cycle, [](const zh_cycle_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == zh_f32_bits(s.t); }, true)) return 1;
+        if (run<PulseOscLayout>(n, make_pulse, [](const zh_pulseosc_state &s, const uint32_t *w, size_t, size_t v) { return w[v] == s.cnt; }, true)) return 1;
+        if (run<EnvelopeLayout>(n, make_envelope, [](const zh_envelope_state &s, const uint32_t *w, size_t n_, size_t v) { return env_rows(s, w + v, n_); }, true)) return 1;
         if (run<PortamentoLayout>(n, make_portamento, [](const zh_portamento_state &s, const uint32_t *w, size_t n_, size_t v) {
                 return w[v] == zh_f32_bits(s.t) && w[n_ + v] == zh_f32_bits(s.last_value) && w[2 * n_ + v] == zh_f32_bits(s.start);
-            })) return 1;
+            }, true)) return 1;
         if (run<DecimatorLayout>(n, make_decimator, [](const zh_decimator_state &s, const uint32_t *w, size_t n_, size_t v) {
                 return w[v] == zh_f32_bits(s.dval) && w[n_ + v] == zh_f32_bits(s.dcount);
-            })) return 1;
+            }, true)) return 1;
         if (run<CurveModuleLayout>(n, make_curve, [](const zh_curve_module_state &s, const uint32_t *w, size_t n_, size_t v) {
                 return w[v] == zh_f32_bits(s.t) && w[n_ + v] == s.current_song_note && (int32_t)w[2 * n_ + v] == s.current_song_note_offset &&
                        s.current_song_note_offset < 0 && w[3 * n_ + v] == s.next_song_note;
-            })) return 1;
+            }, true)) return 1;
         if (run<PmoscLayout>(n, make_pmosc, [](const zh_pmosc_state &s, const uint32_t *w, size_t n_, size_t v) {
                 return w[(size_t)PM_CARRIER_T * n_ + v] == zh_f32_bits(s.carrier.t) && w[(size_t)PM_MODULATOR_T * n_ + v] == zh_f32_bits(s.modulator.t) &&
                        env_rows(s.env, w + (size_t)PM_ENV * n_ + v, n_);
-            })) return 1;
+            }, true)) return 1;
         if (run<FmLayout>(n, make_fm, [](const zh_fm_state &s, const uint32_t *w, size_t n_, size_t v) {
                 for (int op = 0; op < 2; op++) {
                     const zh_fm_op_state &o = op ? s.carrier : s.modulator;
@@ -121,7 +81,7 @@ int main() {
                         r[(size_t)FMS_ELAST * n_] != zh_f32_bits(o.env.last_value) || r[(size_t)FMS_ESTART * n_] != zh_f32_bits(o.env.start)) return false;
                 }
                 return true;
-            })) return 1;
+            }, true)) return 1;
     }
     printf("PASS\n");
     return 0;

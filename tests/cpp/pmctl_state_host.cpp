@@ -3,13 +3,8 @@
 // program for AddressSanitizer + UBSan, as lead_state_host.cpp and dual_state_host.cpp run the other layouts.  For n = 0, 1, 65 and
 // 130 voices: structs -> rows in a heap block of EXACTLY the library's size (kWords * n words) -> structs again, every field
 // compared on bits; and every word of every row is written exactly once, at [word][voice].
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "../../zang_amd/csrc/pmctl.hip.h"
-
-static int fail(const char *what, int a = 0, int b = 0) { printf("%s (%d, %d)\nFAIL\n", what, a, b); return 1; }
+#include "state_harness.h"
 
 static zh_pmctl_state make(uint32_t v) {
     zh_pmctl_state s;
@@ -30,35 +25,18 @@ static void words_of(const zh_pmctl_state &s, uint32_t (&w)[kPmctlState]) {
     memcpy(w, x, sizeof(x));
 }
 
-static int run(size_t n) {
-    using LY = PmctlLayout;
-    std::vector<zh_pmctl_state> in(n), out(n);
-    for (size_t v = 0; v < n; v++) in[v] = make((uint32_t)v);
-    const size_t words = (size_t)LY::kWords * n;
-    uint32_t *w = new uint32_t[words];                                // exactly the library's size
-    for (size_t i = 0; i < words; i++) w[i] = 0xDEADBEEFu;
-    for (size_t v = 0; v < n; v++) LY::pack(in[v], w, n, v);
-    for (size_t i = 0; i < words; i++)
-        if (w[i] == 0xDEADBEEFu) { delete[] w; return fail("a word not written", (int)(i / (n ? n : 1)), (int)(i % (n ? n : 1))); }
-    for (size_t v = 0; v < n; v++) {                                  // [word][voice]: row k holds voice v's word k at column v
-        uint32_t want[kPmctlState];
-        words_of(in[v], want);
-        for (size_t k = 0; k < (size_t)kPmctlState; k++)
-            if (w[k * n + v] != want[k]) { delete[] w; return fail("row layout", (int)v, (int)k); }
-    }
-    for (size_t v = 0; v < n; v++) LY::unpack(out[v], w, n, v);
-    delete[] w;
-    for (size_t v = 0; v < n; v++)
-        if (memcmp(&in[v], &out[v], sizeof(zh_pmctl_state)) != 0) return fail("round trip", (int)v);
-    return 0;
-}
-
 int main() {
     static_assert(kPmctlState == 12 && sizeof(zh_pmctl_state) == 48, "12 words per controlled voice");
     static_assert(PC_RATIO_T == 0 && PC_MULT_T == 3 && PC_CARRIER_T == 6 && PC_MODULATOR_T == 7 && PC_ENV_STATE == 8 && PC_ENV_START == 11,
                   "the rows follow the struct's fields");
     for (size_t n : {(size_t)0, (size_t)1, (size_t)65, (size_t)130})
-        if (run(n)) return 1;
+        if (run<PmctlLayout>(n, make, [](const zh_pmctl_state &s, const uint32_t *w, size_t n_, size_t v) {   // row k holds voice v's word k at column v
+                uint32_t want[kPmctlState];
+                words_of(s, want);
+                for (size_t k = 0; k < (size_t)kPmctlState; k++)
+                    if (w[k * n_ + v] != want[k]) return false;
+                return true;
+            })) return 1;
     printf("PASS\n");
     return 0;
 }

@@ -5,6 +5,7 @@ import numpy as np
 
 from tests import curve_player_reference as cr
 from tests.laser_cases import FIXED, LINEAR, MAX_SPANS, ROWS, SMOOTHSTEP, SPAN, SR, base_image, ms, same_bits  # noqa: F401
+from tests.span_reference import walk
 
 N_EFFECTS = 5
 
@@ -83,11 +84,6 @@ def walked(tb, V):
     S, E = SPAN
     out = []
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), MAX_SPANS)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
+        for k, s, e in walk(tb, v, S, E):
             out.append((v, k, s, e, int(tb["nic"][k, v]), int(tb["effect"][k, v])))
-            i = e
     return out

@@ -9,7 +9,9 @@ import ctypes as C
 
 import numpy as np
 
-from tests.laser_reference import Kit, value  # noqa: F401  (Kit: re-exported for the tests)
+from tests import span_reference as sr
+from tests.laser_reference import Kit  # noqa: F401  (re-exported for the tests)
+from tests.span_reference import state_words, value, walk  # noqa: F401  (state_words: for the tests)
 
 f32 = np.float32
 
@@ -39,13 +41,9 @@ class Voice:
         return out
 
 
-def state_words(voices):
-    return np.array([v.words() for v in voices], np.uint32)
-
-
 def struct_state(st):
     """a modules.CurveVoice.state() array -> [V][10] uint32 words in the same order"""
-    return np.stack([np.ascontiguousarray(st[obj][field]).view(np.uint32) for obj, field in Voice.STATE], axis=1)
+    return sr.struct_state(Voice.STATE, st)
 
 
 def curve_player_paint(o, voice, kit, start, end, out0, out1, temps, nic, sample_rate, rel_freq, effect):
@@ -84,22 +82,15 @@ def paint_spans(o, kit, voices, tb, img0, img1, span, sample_rate, zero_first, d
     image); the walk is the span paints' contract (a sub-span out of order ends the voice's list)."""
     S, E = span
     V, rows = img0.shape
-    K = tb["start"].shape[0]
     temps = [np.zeros(rows, f32) for _ in range(2)]
     if zero_first:
         img0[:, S:E] = 0.0
         if img1 is not None:
             img1[:, S:E] = 0.0
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
-            assert s <= e <= E
+        for k, s, e in walk(tb, v, S, E):
             curve_player_paint(o, voices[v], kit, s, e, img0[v], None if img1 is None else img1[v], temps, tb["nic"][k, v], sample_rate,
                                value(tb, dflt, "rel_freq", k, v), int(value(tb, dflt, "effect", k, v)))
-            i = e
     return img0, img1
 
 

@@ -9,6 +9,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from tests import span_reference as sr
+from tests.span_reference import bits, state_words, value, walk  # noqa: F401  (state_words: for the tests)
+
 f32 = np.float32
 
 
@@ -47,7 +50,6 @@ class Voice:
 
     def words(self):
         """the state as 18 uint32 words: the generator's four u64 as (low, high), then zh_detuned_state's scalars in order"""
-        bits = lambda x: int(np.array([x], f32).view(np.uint32)[0])
         out = []
         for j in range(4):
             out += [int(self.noise.r[j]) & 0xFFFFFFFF, int(self.noise.r[j]) >> 32]
@@ -67,27 +69,17 @@ class Voice:
         self.main_filter.l, self.main_filter.b = float(st["main_filter"]["l"][v]), float(st["main_filter"]["b"][v])
 
 
-def state_words(voices):
-    return np.array([v.words() for v in voices], np.uint32)
-
-
 def struct_state(st):
     """a modules.Detuned.state() array -> [V][18] uint32 words in Voice.words()'s order"""
     r = np.ascontiguousarray(st["noise"]["r"]).astype(np.uint64)                  # [V][4]
     cols = []
     for j in range(4):
         cols += [(r[:, j] & np.uint64(0xFFFFFFFF)).astype(np.uint32), (r[:, j] >> np.uint64(32)).astype(np.uint32)]
-    for obj, field, kind in STATE[1:]:
-        cols.append(np.ascontiguousarray(st[obj][field]).view(np.uint32))
-    return np.stack(cols, axis=1)
+    return np.concatenate([np.stack(cols, axis=1), sr.struct_state(STATE[1:], st)], axis=1)
 
 
 def same_words(a, b):
-    """two [V][18] word arrays: integers equal, floats bit for bit except that any NaN equals any NaN"""
-    fa, fb = a[:, FLOAT_WORDS].view(f32), b[:, FLOAT_WORDS].view(f32)
-    na, nb = np.isnan(fa), np.isnan(fb)
-    return (np.array_equal(a[:, ~FLOAT_WORDS], b[:, ~FLOAT_WORDS]) and np.array_equal(na, nb)
-            and np.array_equal(fa.view(np.uint32)[~na], fb.view(np.uint32)[~nb]))
+    return sr.same_words(FLOAT_WORDS, a, b)
 
 
 def instrument_paint(o, voice, start, end, outputs, temps, nic, sample_rate, freq, freq_warble, note_on, patch):
@@ -135,35 +127,20 @@ def outer_paint(o, voice, start, end, outputs, temps, nic, sample_rate, freq, no
 FIELDS = ("freq", "note_on", "mode")
 
 
-def value(tb, dflt, name, k, v):
-    """field `name` of sub-span k, voice v: the table's array, else the per-voice / broadcast default"""
-    if tb.get(name) is not None:
-        return tb[name][k, v]
-    d = dflt[name]
-    return d[v] if isinstance(d, np.ndarray) else d
-
-
 def paint_spans(o, voices, tb, img, sync, span, sample_rate, zero_first, patch, dflt=None):
     """The Trigger loop (:213-222) of every voice over its sub-spans, in place on img and sync [V][rows] (sync None: outputs[1]
     is not painted); the walk is the span paints' contract (a sub-span out of order ends the voice's list)."""
     S, E = span
     V, rows = img.shape
-    K = tb["start"].shape[0]
     temps = [np.zeros(rows, f32) for _ in range(4)]
     if zero_first:
         img[:, S:E] = 0.0
         if sync is not None:
             sync[:, S:E] = 0.0
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
-            assert s <= e <= E
+        for k, s, e in walk(tb, v, S, E):
             outer_paint(o, voices[v], s, e, (img[v], None if sync is None else sync[v]), temps, tb["nic"][k, v], sample_rate,
                         value(tb, dflt, "freq", k, v), int(value(tb, dflt, "note_on", k, v)) != 0, int(value(tb, dflt, "mode", k, v)), patch)
-            i = e
     return img
 
 

@@ -10,6 +10,9 @@ import ctypes as C
 
 import numpy as np
 
+from tests import span_reference as sr
+from tests.span_reference import state_words, value, walk  # noqa: F401  (state_words: for the tests)
+
 f32 = np.float32
 
 
@@ -61,16 +64,9 @@ class Voice:
         return out
 
 
-def state_words(voices):
-    return np.array([v.words() for v in voices], np.uint32)
-
-
 def struct_state(st):
     """a modules.Laser.state() array -> [V][14] uint32 words in the same order"""
-    cols = []
-    for obj, field in Voice.STATE:
-        cols.append(np.ascontiguousarray(st[obj][field]).view(np.uint32))
-    return np.stack(cols, axis=1)
+    return sr.struct_state(Voice.STATE, st)
 
 
 def laser_paint(o, voice, kit, start, end, out, temps, nic, sample_rate, freq_mul, carrier_mul, modulator_mul, modulator_rad, effect):
@@ -106,33 +102,18 @@ def laser_paint(o, voice, kit, start, end, out, temps, nic, sample_rate, freq_mu
 FIELDS = ("freq_mul", "carrier_mul", "modulator_mul", "modulator_rad", "effect")
 
 
-def value(tb, dflt, name, k, v):
-    """field `name` of sub-span k, voice v: the table's array, else the per-voice / broadcast default"""
-    if tb.get(name) is not None:
-        return tb[name][k, v]
-    d = dflt[name]
-    return d[v] if isinstance(d, np.ndarray) else d
-
-
 def paint_spans(o, kit, voices, tb, img, span, sample_rate, zero_first, dflt=None):
     """The Trigger loop (:149-158) of every voice over its sub-spans, in place on img [V][rows]; the walk is the span paints'
     contract (a sub-span out of order ends the voice's list)."""
     S, E = span
     V, rows = img.shape
-    K = tb["start"].shape[0]
     temps = [np.zeros(rows, f32) for _ in range(3)]
     if zero_first:
         img[:, S:E] = 0.0
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
-            assert s <= e <= E
+        for k, s, e in walk(tb, v, S, E):
             laser_paint(o, voices[v], kit, s, e, img[v], temps, tb["nic"][k, v], sample_rate,
                         *(value(tb, dflt, n, k, v) for n in FIELDS[:4]), int(value(tb, dflt, "effect", k, v)))
-            i = e
     return img
 
 

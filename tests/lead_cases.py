@@ -7,6 +7,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from tests import lead_reference as lr
+from tests.span_reference import walk
 
 SR = 48000.0
 ROWS, SPAN = 256, (3, 250)
@@ -104,15 +105,10 @@ def pairs(tbs):
     for tb in tbs:
         S, E = SPAN
         for v in range(V):
-            i = S
-            for k in range(min(int(tb["count"][v]), MAX_SPANS)):
-                s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-                if s < i or s > E:
-                    break
+            for k, _, _ in walk(tb, v, S, E):
                 on = bool(tb["note_on"][k, v])
                 seen.add((bool(prev[v]), on, bool(tb["nic"][k, v])))
                 prev[v] = on
-                i = e
     return seen
 
 

@@ -9,6 +9,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from tests import span_reference as sr
+from tests.span_reference import bits as _bits, state_words, value, walk  # noqa: F401  (state_words: for the tests)
+
 f32 = np.float32
 CURVE_CUBED = 3
 
@@ -28,9 +31,6 @@ class VibratoPatch:                                # zh_vibrato_patch
     vib_hz: float = 4.0
     depth: float = 0.02
     color: float = 0.5
-
-
-_bits = lambda x: int(np.array([x], f32).view(np.uint32)[0])
 
 
 class PortaVoice:
@@ -74,25 +74,13 @@ class VibratoVoice:
         self.vib.t, self.osc.cnt = float(st["vib"]["t"][v]), int(st["osc"]["cnt"][v])
 
 
-def float_words(cls):
-    return np.array([k == "f" for _, _, k in cls.STATE])
-
-
-def state_words(voices):
-    return np.array([v.words() for v in voices], np.uint32)
-
-
 def struct_state(cls, st):
     """a modules.Porta / Vibrato .state() array -> [V][words] uint32 in cls.words()'s order"""
-    return np.stack([np.ascontiguousarray(st[f] if obj is None else st[obj][f]).view(np.uint32) for obj, f, _ in cls.STATE], axis=1)
+    return sr.struct_state(cls.STATE, st)
 
 
 def same_words(cls, a, b):
-    """two [V][words] arrays: integers equal, floats bit for bit except that any NaN equals any NaN"""
-    fw = float_words(cls)
-    fa, fb = a[:, fw].view(f32), b[:, fw].view(f32)
-    na, nb = np.isnan(fa), np.isnan(fb)
-    return (np.array_equal(a[:, ~fw], b[:, ~fw]) and np.array_equal(na, nb) and np.array_equal(fa.view(np.uint32)[~na], fb.view(np.uint32)[~nb]))
+    return sr.same_words(sr.float_words(cls.STATE), a, b)
 
 
 def porta_paint(o, voice, start, end, outputs, temps, nic, sample_rate, freq, note_on, patch):
@@ -138,36 +126,21 @@ def vibrato_paint(o, voice, start, end, outputs, temps, nic, sample_rate, freq, 
 FIELDS = ("freq", "note_on")
 
 
-def value(tb, dflt, name, k, v):
-    """field `name` of sub-span k, voice v: the table's array, else the per-voice / broadcast default"""
-    if tb.get(name) is not None:
-        return tb[name][k, v]
-    d = dflt[name]
-    return d[v] if isinstance(d, np.ndarray) else d
-
-
 def paint_spans(o, paint, voices, tb, img, sync, span, sample_rate, zero_first, patch, dflt=None):
     """The Trigger loop of every voice over its sub-spans, in place on img and sync [V][rows] (sync None: outputs[1] is not
     painted); `paint` = porta_paint or vibrato_paint; the walk is the span paints' contract (a sub-span out of order ends the
     voice's list)."""
     S, E = span
     V, rows = img.shape
-    K = tb["start"].shape[0]
     temps = [np.zeros(rows, f32) for _ in range(3)]
     if zero_first:
         img[:, S:E] = 0.0
         if sync is not None:
             sync[:, S:E] = 0.0
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
-            assert s <= e <= E
+        for k, s, e in walk(tb, v, S, E):
             paint(o, voices[v], s, e, (img[v], None if sync is None else sync[v]), temps, tb["nic"][k, v], sample_rate,
                   value(tb, dflt, "freq", k, v), int(value(tb, dflt, "note_on", k, v)) != 0, patch)
-            i = e
     return img
 
 

@@ -12,8 +12,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from tests.subsong_reference import ImpulseQueue
-from tests.two_reference import Trigger
+from tests import span_reference as sr
+from tests.span_reference import ImpulseQueue, Trigger, bits as _bits, state_words, walk  # noqa: F401  (state_words, walk: for the tests)
 
 f32 = np.float32
 CURVE_LINEAR, CURVE_CUBED = 1, 3
@@ -30,9 +30,6 @@ class Patch:                                       # zh_pmctl_patch; the default
     decay: float = 0.1
     release: float = 1.0
     sustain_volume: float = 0.5
-
-
-_bits = lambda x: int(np.array([x], f32).view(np.uint32)[0])
 
 
 class Voice:
@@ -62,25 +59,13 @@ class Voice:
         self.carrier.t, self.modulator.t = float(st["carrier"]["t"][v]), float(st["modulator"]["t"][v])
 
 
-def float_words():
-    return np.array([k == "f" for _, _, k in Voice.STATE])
-
-
-def state_words(voices):
-    return np.array([v.words() for v in voices], np.uint32)
-
-
 def struct_state(st):
     """a modules.PMCtl.state() array -> [V][words] uint32 in Voice.words()'s order"""
-    return np.stack([np.ascontiguousarray(st[obj][f]).view(np.uint32) for obj, f, _ in Voice.STATE], axis=1)
+    return sr.struct_state(Voice.STATE, st)
 
 
 def same_words(a, b):
-    """two [V][words] arrays: integers equal, floats bit for bit except that any NaN equals any NaN"""
-    fw = float_words()
-    fa, fb = np.ascontiguousarray(a[:, fw]).view(f32), np.ascontiguousarray(b[:, fw]).view(f32)
-    na, nb = np.isnan(fa), np.isnan(fb)
-    return bool(np.array_equal(a[:, ~fw], b[:, ~fw]) and np.array_equal(na, nb) and np.array_equal(fa.view(np.uint32)[~na], fb.view(np.uint32)[~nb]))
+    return sr.same_words(sr.float_words(Voice.STATE), a, b)
 
 
 def osc_paint(o, voice, start, end, out, temps, nic, sample_rate, freq, relative, ratio, multiplier):
@@ -129,25 +114,11 @@ def control_paint(o, porta, start, end, row, nic, sample_rate, value, scale, not
                                 o.curve(int(patch.ctl_curve), f32(patch.ctl_glide)), float(goal), int(bool(note_on)), 1)
 
 
-def walk(tb, v, S, E):
-    """the rows of voice v a span paint reaches, under the span paints' contract: the first min(count, K); a row that starts
-    before the previous one ends, before S or after E ends the list -> [(k, start, end)]"""
-    out, i = [], S
-    for k in range(min(int(tb["count"][v]), tb["start"].shape[0])):
-        s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-        if s < i or s > E:
-            break
-        assert s <= e <= E
-        out.append((k, s, e))
-        i = e
-    return out
-
-
 def segments(tables, v, S, E):
     """the three-cursor walk's model for one voice: the events and segments the kernel's walk makes without a wave around it
     -> [("begin", stream, k) | ("end", stream) | ("seg", f0, f1, mask)]; at one frame: ends and begins stream by stream (notes,
     ratio, multiplier), a stream's end before its next begin"""
-    rows = [walk(tb, v, S, E) for tb in tables]
+    rows = [walk(tb, v, S, E) for tb in tables]                                    # the span paints' contract, stream by stream
     idx, active, ev = [0, 0, 0], [False, False, False], []
 
     def advance(i):

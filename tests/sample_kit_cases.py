@@ -6,6 +6,8 @@ import ctypes as C
 
 import numpy as np
 
+from tests.span_reference import value, walk  # noqa: F401  (value: for the tests)
+
 ROWS, SPAN = 128, (5, 101)
 MAX_SPANS = 4
 RATES = [44100.0, 44100.5, 22050.0, -44100.0, -22050.0, 48000.0]
@@ -83,35 +85,20 @@ def oracle_params(o, samples, sample, channel, rate, loop):
     return o.SamplerParams(float(rate), nch, in_rate, fmt, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size, int(channel), int(bool(loop)))
 
 
-def value(tb, dflt, name, k, v):
-    """field `name` of sub-span k, voice v: the table's array, else the per-voice / broadcast default"""
-    if tb.get(name) is not None:
-        return tb[name][k, v]
-    d = dflt[name]
-    return d[v] if isinstance(d, np.ndarray) else d
-
-
 def reference(o, samples, tb, t, img, zero_first, span=SPAN, dflt=None):
     """What the span paint must leave: img [V][rows] and t [V], painted in place.  The walk is the span paints' contract."""
     L = o.lib()
     S, E = span
     V = len(tb["count"])
-    K = tb["start"].shape[0]
     if zero_first:
         img[:, S:E] = 0.0
     for v in range(V):
         st = o.Sampler(); st.t = float(t[v])
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
+        for k, s, e in walk(tb, v, S, E):
             p = oracle_params(o, samples, int(value(tb, dflt, "sample", k, v)), value(tb, dflt, "channel", k, v),
                               value(tb, dflt, "sample_rate", k, v), value(tb, dflt, "loop", k, v))
-            assert s <= e <= E
             if p is not None:
                 L.zo_sampler_paint(C.byref(st), s, e, o.fptr(img[v]), int(tb["nic"][k, v]), C.byref(p))
-            i = e
         t[v] = st.t
     return img, t
 

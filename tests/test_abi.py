@@ -59,17 +59,8 @@ def test_struct_sizes_match_c_layout():
              "zh_decimator_params": abi.DecimatorParams, "zh_distortion_params": abi.DistortionParams,
              "zh_nice_params": abi.NiceParams, "zh_nice_state": abi.NiceState, "zh_pmosc_params": abi.PMOscParams,
              "zh_pmosc_state": abi.PMOscState, "zh_trisawosc_state": abi.TriSawOscState, "zh_script_param": abi.ScriptParam}
-    prog = '#include <stdio.h>\n#include "zang_hip.h"\nint main(void){' + "".join(
-        f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "s.c"); exe = os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    for line in out.splitlines():
-        n, sz = line.split()
-        assert C.sizeof(names[n]) == int(sz), (n, C.sizeof(names[n]), sz)
+    from tests.hostprog import mirror_layout
+    mirror_layout(names, offsets=False)
 
 
 def test_product_has_no_oracle_or_cpu_path():

@@ -9,6 +9,7 @@ import pytest
 
 from tests import arp_cases as ac
 from tests import arp_reference as ar
+from tests.hostprog import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "arp_lane_host.cpp")
@@ -17,10 +18,7 @@ PLAYERS = 66
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("arp_lane") / "arp_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("arp_lane"))
 
 
 def _bits(x):

@@ -9,6 +9,7 @@ import subprocess
 
 import numpy as np
 import pytest
+from tests.hostprog import build_linked, fnv1a, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "curve_player_host.cpp")
@@ -16,40 +17,22 @@ EXE = os.path.join(ROOT, "tests", "cpp", "curve_player_host")
 STATE_SRC = os.path.join(ROOT, "tests", "cpp", "curve_player_state_host.cpp")
 
 
-def _build():
-    import zang_amd  # noqa: F401  (fails loudly if libzang_hip.so is missing)
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
-                           "-L" + os.path.join(ROOT, "zang_amd"), "-lzang_hip", "-Wl,-rpath," + os.path.join(ROOT, "zang_amd"),
-                           "-L" + rocm + "/lib", "-Wl,-rpath," + rocm + "/lib", "-o", EXE])
-
-
 def test_curve_player_host_program_compiles_and_links():
-    _build()
+    build_linked(SRC, EXE)
     assert os.path.exists(EXE)
 
 
 def test_state_layout_under_the_sanitizers(tmp_path):
     """1, 3 and 65 voices packed into a heap block of exactly the library's size and read back: every word written once, at
     [word][voice] in the struct's own order; every field of zh_curve_player_state back on bits"""
-    exe = str(tmp_path / "curve_player_state_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           STATE_SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
-
-
-def _fnv1a(h, data):
-    for b in data:
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
+    run_sanitized(STATE_SRC, tmp_path)
 
 
 @pytest.mark.gpu
 def test_curve_player_host_program_paints_what_ctypes_paints(ctx):
     from tests.util import from_image
     from zang_amd import modules as mod, sfx, zang
-    _build()
+    build_linked(SRC, EXE)
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout + r.stderr
     theirs = int(re.search(r"checksum ([0-9a-f]{16})", r.stdout).group(1), 16)
@@ -73,6 +56,6 @@ def test_curve_player_host_program_paints_what_ctypes_paints(ctx):
     ctx.sync()
     ours = 0xCBF29CE484222325
     for data in (*first, from_image(img).tobytes(), from_image(sync).tobytes(), m.state().tobytes()):
-        ours = _fnv1a(ours, data)
+        ours = fnv1a(ours, data)
     assert ours == theirs, (hex(ours), hex(theirs))
     m.close(); kit.close()

@@ -9,6 +9,7 @@ import subprocess
 
 import numpy as np
 import pytest
+from tests.hostprog import build_linked, fnv1a, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "detuned_host.cpp")
@@ -16,40 +17,22 @@ EXE = os.path.join(ROOT, "tests", "cpp", "detuned_host")
 STATE_SRC = os.path.join(ROOT, "tests", "cpp", "detuned_state_host.cpp")
 
 
-def _build():
-    import zang_amd  # noqa: F401  (fails loudly if libzang_hip.so is missing)
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
-                           "-L" + os.path.join(ROOT, "zang_amd"), "-lzang_hip", "-Wl,-rpath," + os.path.join(ROOT, "zang_amd"),
-                           "-L" + rocm + "/lib", "-Wl,-rpath," + rocm + "/lib", "-o", EXE])
-
-
 def test_detuned_host_program_compiles_and_links():
-    _build()
+    build_linked(SRC, EXE)
     assert os.path.exists(EXE)
 
 
 def test_state_layout_under_the_sanitizers(tmp_path):
     """0, 1, 65 and 130 voices packed into a heap block of exactly the library's size and read back: every word written once, at
     [word][voice]; every field of zh_detuned_state back on bits, the taps as zeros"""
-    exe = str(tmp_path / "detuned_state_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           STATE_SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
-
-
-def _fnv1a(h, data):
-    for b in data:
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
+    run_sanitized(STATE_SRC, tmp_path)
 
 
 @pytest.mark.gpu
 def test_detuned_host_program_paints_what_ctypes_paints(ctx):
     from tests.util import from_image
     from zang_amd import modules as mod, zang
-    _build()
+    build_linked(SRC, EXE)
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout + r.stderr
     theirs = int(re.search(r"checksum ([0-9a-f]{16})", r.stdout).group(1), 16)
@@ -73,7 +56,7 @@ def test_detuned_host_program_paints_what_ctypes_paints(ctx):
     m.paint_spans(zang.Span(S, E), [img, sync], None, p, table, zero_first=True)
     m.paint(zang.Span(S, E), [img], [], False, p)
     ctx.sync()
-    h = _fnv1a(_fnv1a(_fnv1a(0xCBF29CE484222325, first), from_image(img).tobytes()), from_image(sync).tobytes())
-    ours = _fnv1a(h, m.state().tobytes())
+    h = fnv1a(fnv1a(fnv1a(0xCBF29CE484222325, first), from_image(img).tobytes()), from_image(sync).tobytes())
+    ours = fnv1a(h, m.state().tobytes())
     assert ours == theirs, (hex(ours), hex(theirs))
     m.close()

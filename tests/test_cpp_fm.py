@@ -7,36 +7,23 @@ import subprocess
 
 import numpy as np
 import pytest
+from tests.hostprog import build_linked, fnv1a
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "fm_host.cpp")
 EXE = os.path.join(ROOT, "tests", "cpp", "fm_host")
 
 
-def _build():
-    import zang_amd  # noqa: F401  (fails loudly if libzang_hip.so is missing)
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
-                           "-L" + os.path.join(ROOT, "zang_amd"), "-lzang_hip", "-Wl,-rpath," + os.path.join(ROOT, "zang_amd"),
-                           "-L" + rocm + "/lib", "-Wl,-rpath," + rocm + "/lib", "-o", EXE])
-
-
 def test_fm_host_program_compiles_and_links():
-    _build()
+    build_linked(SRC, EXE)
     assert os.path.exists(EXE)
-
-
-def _fnv1a(h, data):
-    for b in data:
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
 
 
 @pytest.mark.gpu
 def test_fm_host_program_paints_what_ctypes_paints(ctx):
     from tests.util import dev, from_image, to_image
     from zang_amd import abi, modules as mod, zang
-    _build()
+    build_linked(SRC, EXE)
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout + r.stderr
     theirs = int(re.search(r"checksum ([0-9a-f]{16})", r.stdout).group(1), 16)
@@ -58,6 +45,6 @@ def test_fm_host_program_paints_what_ctypes_paints(ctx):
     m.paint(zang.Span(0, 200), [img], None, True, m.Params(sr, ti, vi, dev(freq), True))
     m.paint(zang.Span(200, F), [img], None, False, m.Params(sr, ti, vi, dev(freq), False))
     ctx.sync()
-    ours = _fnv1a(_fnv1a(0xCBF29CE484222325, from_image(img).tobytes()), m.state().tobytes())
+    ours = fnv1a(fnv1a(0xCBF29CE484222325, from_image(img).tobytes()), m.state().tobytes())
     assert ours == theirs, (hex(ours), hex(theirs))
     m.close()

@@ -8,6 +8,7 @@ import subprocess
 
 import numpy as np
 import pytest
+from tests.hostprog import build_linked, fnv1a, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "laser_host.cpp")
@@ -15,40 +16,22 @@ EXE = os.path.join(ROOT, "tests", "cpp", "laser_host")
 KIT_SRC = os.path.join(ROOT, "tests", "cpp", "sfx_kit_host.cpp")
 
 
-def _build():
-    import zang_amd  # noqa: F401  (fails loudly if libzang_hip.so is missing)
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
-                           "-L" + os.path.join(ROOT, "zang_amd"), "-lzang_hip", "-Wl,-rpath," + os.path.join(ROOT, "zang_amd"),
-                           "-L" + rocm + "/lib", "-Wl,-rpath," + rocm + "/lib", "-o", EXE])
-
-
 def test_laser_host_program_compiles_and_links():
-    _build()
+    build_linked(SRC, EXE)
     assert os.path.exists(EXE)
 
 
 def test_kit_packing_under_the_sanitizers(tmp_path):
     """three kits (empty curves, one effect, five effects of unequal lengths) packed into a heap block of exactly the library's
     size, descriptors and nodes read back; the refusals of zh_sfx_kit_create"""
-    exe = str(tmp_path / "sfx_kit_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           KIT_SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
-
-
-def _fnv1a(h, data):
-    for b in data:
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
+    run_sanitized(KIT_SRC, tmp_path)
 
 
 @pytest.mark.gpu
 def test_laser_host_program_paints_what_ctypes_paints(ctx):
     from tests.util import from_image
     from zang_amd import modules as mod, sfx, zang
-    _build()
+    build_linked(SRC, EXE)
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout + r.stderr
     theirs = int(re.search(r"checksum ([0-9a-f]{16})", r.stdout).group(1), 16)
@@ -70,6 +53,6 @@ def test_laser_host_program_paints_what_ctypes_paints(ctx):
     m.paint_spans(zang.Span(S, E), [img], None, p, table, zero_first=True)
     m.paint(zang.Span(S, E), [img], [], False, p)
     ctx.sync()
-    ours = _fnv1a(_fnv1a(_fnv1a(0xCBF29CE484222325, first), from_image(img).tobytes()), m.state().tobytes())
+    ours = fnv1a(fnv1a(fnv1a(0xCBF29CE484222325, first), from_image(img).tobytes()), m.state().tobytes())
     assert ours == theirs, (hex(ours), hex(theirs))
     m.close(); kit.close()

@@ -2,7 +2,8 @@
 of module_state.hip.h and fm.hip.h) under AddressSanitizer + UBSan, as a stand-alone program with its own main
 (tests/cpp/module_state_host.cpp): nothing loaded into python runs under a sanitizer."""
 import os
-import subprocess
+
+from tests.hostprog import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "module_state_host.cpp")
@@ -11,8 +12,4 @@ SRC = os.path.join(ROOT, "tests", "cpp", "module_state_host.cpp")
 def test_module_state_layouts_under_the_sanitizers(tmp_path):
     """n = 0, 1, 65, 130: hostile structs -> rows in a heap block of exactly kWords * n words -> structs, bit for bit; every word
     written; the rows the kernels read hold voice v at column v; kWords and sizeof(State) are the numbers of the code they replaced"""
-    exe = str(tmp_path / "module_state_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
+    run_sanitized(SRC, tmp_path)

@@ -10,16 +10,14 @@ import pytest
 
 from tests import mouse_cases as mc
 from tests import mouse_reference as mr
+from tests.hostprog import build_sanitized, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("pmctl_walk") / "pmctl_walk_host")
-    subprocess.check_call(SAN + [os.path.join(ROOT, "tests", "cpp", "pmctl_walk_host.cpp"), "-o", exe])
-    return exe
+    return build_sanitized(os.path.join(ROOT, "tests", "cpp", "pmctl_walk_host.cpp"), tmp_path_factory.mktemp("pmctl_walk"))
 
 
 def _run(exe, text):
@@ -110,7 +108,4 @@ def test_a_count_above_the_tables_rows_is_clamped(harness):
 
 
 def test_the_voices_state_layout_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "pmctl_state_host")
-    subprocess.check_call(SAN + [os.path.join(ROOT, "tests", "cpp", "pmctl_state_host.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
+    run_sanitized(os.path.join(ROOT, "tests", "cpp", "pmctl_state_host.cpp"), tmp_path)

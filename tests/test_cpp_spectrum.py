@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import spectrum_reference as sr
+from tests.hostprog import FNV_BASIS, build_linked, fnv1a
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "spectrum_host.cpp")
@@ -15,23 +16,9 @@ EXE = os.path.join(ROOT, "tests", "cpp", "spectrum_host")
 V, F, W, H = 66, 1024 + 8, 3, 5
 
 
-def _build():
-    import zang_amd  # noqa: F401  (fails loudly if libzang_hip.so is missing)
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
-                           "-L" + os.path.join(ROOT, "zang_amd"), "-lzang_hip", "-Wl,-rpath," + os.path.join(ROOT, "zang_amd"),
-                           "-L" + rocm + "/lib", "-Wl,-rpath," + rocm + "/lib", "-o", EXE])
-
-
 def test_spectrum_host_program_compiles_and_links():
-    _build()
+    build_linked(SRC, EXE)
     assert os.path.exists(EXE)
-
-
-def _fnv1a(data, h=0xCBF29CE484222325):
-    for b in data:
-        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
 
 
 def _image():
@@ -43,19 +30,19 @@ def _image():
 
 def expected_words(oracle):
     img = _image()
-    words = ["plot %016x" % _fnv1a(np.ascontiguousarray(sr.plot(img[3:3 + 1024]).T).tobytes())]
+    words = ["plot %016x" % fnv1a(FNV_BASIS, np.ascontiguousarray(sr.plot(img[3:3 + 1024]).T).tobytes())]
     gram = sr.Spectrogram(V, W, H, sr.oracle_pow10(oracle))
     for b, log in enumerate([False, False, True, True, True]):
         gram.plot(img[2 * b:2 * b + 1024], log)
-        h = _fnv1a(np.ascontiguousarray(gram.buffer).tobytes())
-        words.append("gram %d %d %016x" % (b, gram.drawindex, _fnv1a(np.ascontiguousarray(gram.scrolled()).tobytes(), h)))
+        h = fnv1a(FNV_BASIS, np.ascontiguousarray(gram.buffer).tobytes())
+        words.append("gram %d %d %016x" % (b, gram.drawindex, fnv1a(h, np.ascontiguousarray(gram.scrolled()).tobytes())))
     host = np.ascontiguousarray(img.T).reshape(-1)                     # the program's [voice][frame] array
     re = np.ascontiguousarray(host[:V * 64].reshape(V, 64).T)
     im = np.ascontiguousarray(host[V * 64:2 * V * 64].reshape(V, 64).T)
     r, i = np.ascontiguousarray(re[7:39]), np.ascontiguousarray(im[7:39])
     sr.fft(32, r, i)
     re[7:39], im[7:39] = r, i
-    words.append("fft %016x" % _fnv1a(np.ascontiguousarray(im.T).tobytes(), _fnv1a(np.ascontiguousarray(re.T).tobytes())))
+    words.append("fft %016x" % fnv1a(fnv1a(FNV_BASIS, np.ascontiguousarray(re.T).tobytes()), np.ascontiguousarray(im.T).tobytes()))
     return words
 
 
@@ -71,7 +58,7 @@ def test_the_expected_words_need_no_device(oracle):
 
 @pytest.mark.gpu
 def test_spectrum_host_program_prints_the_yardsticks_words(ctx, oracle):
-    _build()
+    build_linked(SRC, EXE)
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASS"), r.stdout + r.stderr
     assert r.stdout.split("\n")[:7] == expected_words(oracle), r.stdout

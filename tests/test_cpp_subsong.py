@@ -10,6 +10,7 @@ import pytest
 
 from tests import subsong_cases as sc
 from tests import subsong_reference as sr
+from tests.hostprog import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "subsong_lane_host.cpp")
@@ -18,10 +19,7 @@ PLAYERS = 66
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("subsong_lane") / "subsong_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("subsong_lane"), ["-ffp-contract=off"])
 
 
 def _run(exe, text):

@@ -5,16 +5,14 @@ reaching every case the GPU tests rely on."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import curve_player_cases as cc
 from tests import curve_player_reference as cr
+from tests.hostprog import flat_header, mirror_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "zang_hip.h")
 CSRC = os.path.join(ROOT, "zang_amd", "csrc")
 
 DECLS = [
@@ -32,13 +30,8 @@ FIELDS = ["REL_FREQ", "EFFECT"]
 MEMBERS = ["carrier_curve", "carrier", "modulator_curve", "modulator"]
 
 
-def _flat_header():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return " ".join(text.split()).replace(" ,", ",")
-
-
 def test_header_declares_the_entry_points_and_the_field_enum():
-    text = _flat_header()
+    text = flat_header()
     for decl in DECLS:
         assert " ".join(decl.split()) in text, decl
     m = re.search(r"enum \{ (ZH_CURVE_PLAYER_SPAN_REL_FREQ = 0.*?) \};", text)
@@ -77,18 +70,7 @@ def test_ctypes_mirror_and_python_fields_follow_the_header():
 def test_struct_sizes_match_gcc():
     from zang_amd import abi
     names = {"zh_curve_player_params": abi.CurvePlayerParams, "zh_curve_player_state": abi.CurvePlayerState}
-    prog = '#include <stdio.h>\n#include "zang_hip.h"\nint main(void){' + "".join(
-        f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        n, sz = line.split()
-        seen[n] = int(sz)
-        assert C.sizeof(names[n]) == int(sz), (n, C.sizeof(names[n]), sz)
+    seen = {n: size for n, (size, _) in mirror_layout(names, offsets=False)[0].items()}
     assert sorted(seen) == sorted(names) and seen["zh_curve_player_state"] == 40            # ten words per voice
 
 

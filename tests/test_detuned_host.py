@@ -5,16 +5,14 @@ over one full sub-span is its plain paint, the planted warble reaches pow's arms
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import detuned_cases as dc
 from tests import detuned_reference as dr
+from tests.hostprog import flat_header, mirror_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "zang_hip.h")
 
 DECLS = [
     "ZH_API int zh_detuned_patch_default(zh_detuned_patch *patch);",
@@ -31,13 +29,8 @@ FIELDS = ["FREQ", "NOTE_ON", "MODE"]
 PATCH_FIELDS = ["warble_hz", "warble_wide", "color", "volume", "attack", "decay", "release", "sustain_volume", "cutoff_hz", "res"]
 
 
-def _flat_header():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return " ".join(text.split()).replace(" ,", ",")
-
-
 def test_header_declares_the_entry_points_and_the_field_enum():
-    text = _flat_header()
+    text = flat_header()
     for decl in DECLS:
         assert " ".join(decl.split()) in text, decl
     m = re.search(r"enum \{ (ZH_DETUNED_SPAN_FREQ = 0.*?) \};", text)
@@ -72,23 +65,7 @@ def test_ctypes_mirror_and_python_fields_follow_the_header():
 def test_struct_sizes_and_offsets_match_gcc():
     from zang_amd import abi
     names = {"zh_detuned_patch": abi.DetunedPatch, "zh_detuned_params": abi.DetunedParams, "zh_detuned_state": abi.DetunedState}
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "zang_hip.h"\nint main(void){'
-    for n, t in names.items():
-        prog += f'printf("{n} - %zu\\n", sizeof({n}));'
-        for f, _ in t._fields_:
-            prog += f'printf("{n} {f} %zu\\n", offsetof({n}, {f}));'
-    prog += "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    seen = 0
-    for line in out.splitlines():
-        n, f, x = line.split()
-        want = C.sizeof(names[n]) if f == "-" else getattr(names[n], f).offset
-        assert want == int(x), (n, f, want, x)
-        seen += 1
+    _, seen = mirror_layout(names)
     assert seen == 3 + 10 + 6 + 5 and C.sizeof(abi.DetunedState) == 104 and C.sizeof(abi.DetunedPatch) == 40
 
 

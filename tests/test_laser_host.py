@@ -5,17 +5,15 @@ triple, and the shared tables reaching every case the GPU tests rely on."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import laser_cases as lc
 from tests import laser_reference as lr
+from tests.hostprog import flat_header, mirror_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "zang_hip.h")
 
 DECLS = [
     "ZH_API int zh_sfx_effect_default(zh_sfx_effect *effect, zh_curve_node *nodes );",
@@ -35,13 +33,8 @@ DECLS = [
 FIELDS = ["FREQ_MUL", "CARRIER_MUL", "MODULATOR_MUL", "MODULATOR_RAD", "EFFECT"]
 
 
-def _flat_header():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return " ".join(text.split()).replace(" ,", ",")
-
-
 def test_header_declares_the_entry_points_and_the_field_enum():
-    text = _flat_header()
+    text = flat_header()
     for decl in DECLS:
         assert " ".join(decl.split()) in text, decl
     m = re.search(r"enum \{ (ZH_LASER_SPAN_FREQ_MUL = 0.*?) \};", text)
@@ -79,18 +72,7 @@ def test_ctypes_mirror_and_python_fields_follow_the_header():
 def test_struct_sizes_match_gcc():
     from zang_amd import abi
     names = {"zh_sfx_curve": abi.SfxCurve, "zh_sfx_effect": abi.SfxEffect, "zh_laser_params": abi.LaserParams, "zh_laser_state": abi.LaserState}
-    prog = '#include <stdio.h>\n#include "zang_hip.h"\nint main(void){' + "".join(
-        f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        n, sz = line.split()
-        seen[n] = int(sz)
-        assert C.sizeof(names[n]) == int(sz), (n, C.sizeof(names[n]), sz)
+    seen = {n: size for n, (size, _) in mirror_layout(names, offsets=False)[0].items()}
     assert sorted(seen) == sorted(names) and seen["zh_laser_state"] == 56
 
 

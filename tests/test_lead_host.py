@@ -5,17 +5,15 @@ sanitizer) -- the portamento example's key rule alone, and the yardstick's own c
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import lead_cases as lc
 from tests import lead_reference as lr
+from tests.hostprog import flat_header, mirror_layout, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "zang_hip.h")
 STATE_SRC = os.path.join(ROOT, "tests", "cpp", "lead_state_host.cpp")
 NAMES = ("porta", "vibrato")
 
@@ -39,14 +37,9 @@ PATCH_FIELDS = {"porta": ["glide_curve", "glide", "attack", "decay", "release", 
 STATE_FIELDS = {"porta": ["porta", "env", "osc", "prev_note_on"], "vibrato": ["vib", "osc"]}
 
 
-def _flat_header():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return " ".join(text.split()).replace(" ,", ",")
-
-
 @pytest.mark.parametrize("x", NAMES)
 def test_header_declares_the_entry_points_and_the_field_enum(x):
-    text = _flat_header()
+    text = flat_header()
     for decl in _decls(x):
         assert " ".join(decl.split()) in text, decl
     X = x.upper()
@@ -88,23 +81,7 @@ def test_ctypes_mirror_and_python_fields_follow_the_header(x):
 def test_struct_sizes_and_offsets_match_gcc():
     from zang_amd import abi
     names = {f"zh_{x}_{s}": getattr(abi, x.capitalize() + s.capitalize()) for x in NAMES for s in ("patch", "params", "state")}
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "zang_hip.h"\nint main(void){'
-    for n, t in names.items():
-        prog += f'printf("{n} - %zu\\n", sizeof({n}));'
-        for f, _ in t._fields_:
-            prog += f'printf("{n} {f} %zu\\n", offsetof({n}, {f}));'
-    prog += "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    seen = 0
-    for line in out.splitlines():
-        n, f, x = line.split()
-        want = C.sizeof(names[n]) if f == "-" else getattr(names[n], f).offset
-        assert want == int(x), (n, f, want, x)
-        seen += 1
+    _, seen = mirror_layout(names)
     assert seen == 6 + (6 + 5 + 4) + (3 + 5 + 2)
     assert C.sizeof(abi.PortaState) == 36 and C.sizeof(abi.VibratoState) == 8 and C.sizeof(abi.PortaPatch) == 24 and C.sizeof(abi.VibratoPatch) == 12
 
@@ -149,11 +126,7 @@ def test_state_layouts_under_the_sanitizers(tmp_path):
     """0, 1, 65 and 130 voices of both leads -- and of the four other voices on the same host side: HardSquare, SawEnv, detuned,
     laser -- packed into heap blocks of exactly the library's size and read back: every word written once, at [word][voice]; every
     field of the six state structs back on bits"""
-    exe = str(tmp_path / "lead_state_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           STATE_SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and not r.stderr and r.stdout.strip().endswith("PASS"), r.stdout[-2000:] + r.stderr[-4000:]
+    run_sanitized(STATE_SRC, tmp_path)
 
 
 # ------------------------------------------------------------------ the key rule alone

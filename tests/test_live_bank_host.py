@@ -10,6 +10,7 @@ import pytest
 
 from tests import live_bank_cases as lb
 from tests import voice_bank_cases as vb
+from tests.hostprog import build_sanitized
 
 SRC = os.path.join(lb.ROOT, "tests", "cpp", "live_lane_host.cpp")
 N_INST = 32                                      # instruments 15 and 31 of the corpus push 40 per buffer
@@ -17,10 +18,7 @@ N_INST = 32                                      # instruments 15 and 31 of the 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("live_lane") / "live_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("live_lane"))
 
 
 def _run(exe, args, text=None):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import mix_groups_cases as mg
+from tests.hostprog import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "mix_lane_host.cpp")
@@ -52,10 +53,7 @@ def test_refusals_that_need_no_device():
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mix_lane") / "mix_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("mix_lane"))
 
 
 def _through_harness(exe, tmp, img, stride, P, start_rows, span, zero_first, s16, nch, ch, vol):

@@ -7,14 +7,13 @@ Sampler._paint_kit_spans builds the right call."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 import wave
 
 import numpy as np
 import pytest
 
 from tests import sample_kit_cases as sk
+from tests.hostprog import build_sanitized, flat_header, mirror_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "sample_kit_lane_host.cpp")
@@ -36,10 +35,7 @@ FIELDS = ["SAMPLE_RATE", "LOOP", "SAMPLE", "CHANNEL"]
 # ------------------------------------------------------------------ the lane under the sanitizers
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("sample_kit_lane") / "sample_kit_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("sample_kit_lane"))
 
 
 @pytest.mark.parametrize("V", [1, 65, 130])
@@ -82,13 +78,8 @@ def test_the_test_tables_reach_every_case_the_issue_names():
 
 
 # ------------------------------------------------------------------ header, mirror, binding
-def _flat_header():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return " ".join(text.split()).replace(" ,", ",")
-
-
 def test_header_declares_the_entry_points_and_the_field_enum():
-    text = _flat_header()
+    text = flat_header()
     for decl in DECLS:
         assert " ".join(decl.split()) in text, decl
     m = re.search(r"enum \{ (ZH_SAMPLER_KIT_SPAN_SAMPLE_RATE = 0.*?) \};", text)
@@ -120,18 +111,7 @@ def test_ctypes_mirror_and_python_fields_follow_the_header():
 def test_struct_sizes_match_gcc():
     from zang_amd import abi
     names = {"zh_u32": abi.U32, "zh_sampler_kit_params": abi.SamplerKitParams, "zh_sample": abi.Sample}
-    prog = '#include <stdio.h>\n#include "zang_hip.h"\nint main(void){' + "".join(
-        f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        n, sz = line.split()
-        seen[n] = int(sz)
-        assert C.sizeof(names[n]) == int(sz), (n, C.sizeof(names[n]), sz)
+    seen = {n: size for n, (size, _) in mirror_layout(names, offsets=False)[0].items()}
     assert sorted(seen) == sorted(names)
 
 

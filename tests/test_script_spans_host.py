@@ -5,13 +5,12 @@ hand-made lists and zh_poly_voice schedules as the [span][voice] arrays the kern
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from tests import script_fuzz
+from tests.hostprog import c_ints, c_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CORPUS = [os.path.join(ROOT, "tests", "golden", "script_modules.txt"), os.path.join(ROOT, "tests", "golden", "example_script.txt")]
@@ -75,21 +74,12 @@ def test_spans_form_of_random_scripts_compiles_for_gfx950(seed):
 
 def test_struct_layouts_match_the_c_compiler():
     from zang_amd import abi
-    prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "zang_hip.h"\nint main(void){'
-            'printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(zh_script_span_table), offsetof(zh_script_span_table, max_spans), '
-            'offsetof(zh_script_span_table, count), offsetof(zh_script_span_table, start), offsetof(zh_script_span_table, end), '
-            'offsetof(zh_script_span_table, note_id_changed));'
-            'printf("%zu %zu %zu\\n", sizeof(zh_script_span_param), offsetof(zh_script_span_param, f), offsetof(zh_script_span_param, u));'
-            'printf("%d\\n", ZH_ZSCRIPT_FORM_SPANS);return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
     T, P = abi.ScriptSpanTable, abi.ScriptSpanParam
-    assert [int(x) for x in out[0].split()] == [C.sizeof(T), T.max_spans.offset, T.count.offset, T.start.offset, T.end.offset, T.note_id_changed.offset]
-    assert [int(x) for x in out[1].split()] == [C.sizeof(P), P.f.offset, P.u.offset]
-    assert int(out[2]) == abi.ZSCRIPT_FORM_SPANS
+    lay = c_layout({"zh_script_span_table": ["max_spans", "count", "start", "end", "note_id_changed"], "zh_script_span_param": ["f", "u"]})
+    assert lay["zh_script_span_table"] == (C.sizeof(T), {"max_spans": T.max_spans.offset, "count": T.count.offset, "start": T.start.offset,
+                                                         "end": T.end.offset, "note_id_changed": T.note_id_changed.offset})
+    assert lay["zh_script_span_param"] == (C.sizeof(P), {"f": P.f.offset, "u": P.u.offset})
+    assert c_ints(["ZH_ZSCRIPT_FORM_SPANS"]) == [abi.ZSCRIPT_FORM_SPANS]
     from zang_amd import zscript_native as native
     assert native.FORM_SPANS == abi.ZSCRIPT_FORM_SPANS
 

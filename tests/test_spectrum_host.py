@@ -16,6 +16,7 @@ import pytest
 from tests import spectrum_cases as sc
 from tests import spectrum_reference as sr
 from tests.hostile_cases import same_f32
+from tests.hostprog import build_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "zang_hip.h")
@@ -101,10 +102,7 @@ def test_twiddle_table_is_the_references_on_bits_and_smaller_tables_are_prefixes
 # ------------------------------------------------------------------ the lane harness, sanitized
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("fft_lane") / "fft_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", LANE_SRC, "-o", exe])
-    return exe
+    return build_sanitized(LANE_SRC, tmp_path_factory.mktemp("fft_lane"), ["-ffp-contract=off"])
 
 
 def _run(exe, mode, head, arrays, tmp_path):

@@ -3,12 +3,12 @@
 mirror and struct sizes agree."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import two_reference as tr
+from tests.hostprog import c_ints, mirror_layout
 
 f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,24 +58,9 @@ def test_records_and_source_descriptors():
 def test_struct_sizes_match_gcc(tmp_path):
     from zang_amd import abi
     names = {"zh_span_merge_source": abi.SpanMergeSource, "zh_dual_patch": abi.DualPatch, "zh_dual_params": abi.DualParams, "zh_dual_state": abi.DualState}
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "zang_hip.h"\nint main(void){'
-    for n, t in names.items():
-        prog += f'printf("{n} - %zu\\n", sizeof({n}));'
-        for f, _ in t._fields_:
-            prog += f'printf("{n} {f} %zu\\n", offsetof({n}, {f}));'
-    prog += 'printf("own - %d\\n", ZH_SPAN_MERGE_OWN_FIELDS * 100 + ZH_SPAN_MERGE_NIC_B * 10 + ZH_SPAN_MERGE_NIC_A); return 0;}'
-    src, exe = str(tmp_path / "s.c"), str(tmp_path / "s")
-    open(src, "w").write(prog)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    seen = 0
-    for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
-        n, f, x = line.split()
-        if n == "own":
-            assert int(x) == 321 == abi.SPAN_MERGE_OWN_FIELDS * 100 + abi.SPAN_MERGE_NIC_B * 10 + abi.SPAN_MERGE_NIC_A
-            continue
-        want = C.sizeof(names[n]) if f == "-" else getattr(names[n], f).offset
-        assert want == int(x), (n, f, want, x)
-        seen += 1
+    own, = c_ints(["ZH_SPAN_MERGE_OWN_FIELDS * 100 + ZH_SPAN_MERGE_NIC_B * 10 + ZH_SPAN_MERGE_NIC_A"])
+    assert own == 321 == abi.SPAN_MERGE_OWN_FIELDS * 100 + abi.SPAN_MERGE_NIC_B * 10 + abi.SPAN_MERGE_NIC_A
+    _, seen = mirror_layout(names)
     assert seen == 4 + 3 + 4 + 6 + 2
 
 

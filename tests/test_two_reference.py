@@ -41,8 +41,21 @@ def test_the_case_list_holds_what_the_mutants_need():
 
 
 def test_main_modules_triggers_feed_the_same_loop(oracle):
-    """MainModule's rows for scripted key events == the loop over the two Triggers' full sub-span lists as tables"""
-    from tests.subsong_reference import Trigger as ListTrigger
+    """MainModule's rows for scripted key events == the loop over the two Triggers' full sub-span lists as tables.  The lists come
+    from a second body of trigger.zig, the library's host Trigger (zh_trigger_*), since the model's two faces share one."""
+    from tests.lead_reference import Note                                      # (freq f32, note_on u32): the shape of both records
+    from zang_amd import notes
+    from zang_amd.zang import Span
+
+    class ListTrigger:
+        def __init__(self):
+            self.t = notes.Trigger(Note)()
+
+        def spans(self, start, end, impulses):
+            iap = notes.ImpulsesAndParamses([notes.Impulse(f, i, 0) for f, i, _ in impulses], [Note(p[0], int(p[1])) for _, _, p in impulses])
+            ctr = self.t.counter(Span(start, end), iap)
+            return [(r.span.start, r.span.end, (r.params.freq, r.params.note_on), r.note_id_changed) for r in iter(lambda: self.t.next(ctr), None)]
+
     m = tr.MainModule(oracle)
     events = [(0, "k", 10, True, 30), (0, "n", 3, True, 30), (0, "k", 10, False, 90), (1, "k", 11, True, 0), (1, "n", 3, False, 17),
               (1, "n", 4, False, 40), (2, "k", 12, True, 255)]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import voice_bank_cases as vb
+from tests.hostprog import build_sanitized
 
 ROOT = vb.ROOT
 SRC = os.path.join(ROOT, "tests", "cpp", "sched_lane_host.cpp")
@@ -15,10 +16,7 @@ SRC = os.path.join(ROOT, "tests", "cpp", "sched_lane_host.cpp")
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("sched_lane") / "sched_lane_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           SRC, "-o", exe])
-    return exe
+    return build_sanitized(SRC, tmp_path_factory.mktemp("sched_lane"))
 
 
 def _run(exe, args, text=None):

@@ -1,6 +1,6 @@
 """The yardstick of the two-source tests; holds no tests.  examples/example_two.zig restated line by line in numpy f32, from the Zig
-alone: MainModule.paint (:65-154) -- the `first` pushes, the two Triggers (src/zang/trigger.zig:26-198, here with `next` as the
-reference has it: one sub-span per call), the merge loop of :93-151, the oracle's TriSawOsc and Envelope paints, zang.zero,
+alone: MainModule.paint (:65-154) -- the `first` pushes, the two Triggers (src/zang/trigger.zig:26-198: tests/span_reference.py's, through `next` as the
+reference has it, one sub-span per call), the merge loop of :93-151, the oracle's TriSawOsc and Envelope paints, zang.zero,
 zang.multiply and zang.addScalarInto -- and keyEvent (:156-177).  The merge loop exists once (merge_loop) and runs over two `next`
 callables: the Triggers' for MainModule, the rows of two tables for the stage's model (merge_table).
 Where the reference is undefined: a sub-span whose end is at or below the loop's position, or above the span's end (no Trigger
@@ -9,56 +9,14 @@ import ctypes as C
 
 import numpy as np
 
-from tests.subsong_reference import ImpulseQueue, bits, curve_cubed
+from tests import span_reference as sr
+from tests.span_reference import ImpulseQueue, Trigger, bits, value, walk  # noqa: F401  (Trigger: for the tests)
+from tests.subsong_reference import curve_cubed
 
 f32 = np.float32
 A4 = 880.0                                         # :21
 SAMPLE_RATE = 48000                                # :8
 DEFAULT_PATCH = (0.025, 0.1, 1.0, 0.5)             # attack / decay / release :132-134 (cubed), sustain_volume :135
-
-
-class Trigger:
-    """trigger.zig:26-198; `note` = (id, params) or None.  counter() + next() as the reference: next -> (start, end, params,
-    note_id_changed) or None"""
-
-    def __init__(self):
-        self.note = None
-
-    def counter(self, start, end, impulses):                                   # :62-70
-        return {"pos": start, "end": end, "impulses": impulses, "idx": 0}
-
-    def next(self, ctr):                                                       # :80-105
-        imp = ctr["impulses"]
-        while ctr["pos"] < ctr["end"]:
-            pos, end, span = ctr["pos"], ctr["end"], None
-            if self.note is not None:                                          # carryOver :107-137
-                if ctr["idx"] < len(imp):
-                    nf = imp[ctr["idx"]][0]
-                    if nf > pos:
-                        span = (pos, min(end, nf), self.note)
-                else:
-                    span = (pos, end, self.note)
-            if span is None:                                                   # getNextNoteSpan :139-196
-                span = (pos, end, None)
-                while ctr["idx"] < len(imp):
-                    frame, note_id, params = imp[ctr["idx"]]
-                    if frame >= end:                                           # :144-150
-                        break
-                    if frame > pos:                                            # :152-159
-                        span = (pos, frame, None)
-                        break
-                    ctr["idx"] += 1                                            # :163
-                    clipped = min(end, imp[ctr["idx"]][0]) if ctr["idx"] < len(imp) else end   # :167-171
-                    if clipped <= pos:                                         # :173-178
-                        continue
-                    span = (pos, clipped, (note_id, params))
-                    break
-            ctr["pos"] = span[1]                                               # :88
-            if span[2] is not None:                                            # :90-100
-                changed = True if self.note is None else span[2][0] != self.note[0]
-                self.note = span[2]
-                return (span[0], span[1], span[2][1], changed)
-        return None
 
 
 def merge_loop(next0, next1, start, end):
@@ -144,14 +102,10 @@ def merge_table(players_a, on_a, players_b, on_b, out_len, max_spans, n_out):
 
 def same_table(got, ref):
     """counts equal, and every row below a player's count equal; -> None or what differs first"""
-    if not np.array_equal(got["count"], ref["count"]):
-        return ("count", np.argwhere(got["count"] != ref["count"])[:4].tolist())
-    K = ref["start"].shape[0]
-    live = np.arange(K)[:, None] < ref["count"][None, :]
-    for name in ("start", "end", "nic"):
-        a, b = got[name][:K], ref[name]
-        if not np.array_equal(a[live], b[live]):
-            return (name, np.argwhere((a != b) & live)[:4].tolist())
+    diff = sr.same_table(got, ref, ("start", "end", "nic"))
+    if diff is not None:
+        return diff
+    K, live = ref["start"].shape[0], sr.live_rows(ref)
     for f in range(ref["words"].shape[0]):
         a, b = got["words"][f][:K], ref["words"][f]
         if not np.array_equal(a[live], b[live]):
@@ -197,35 +151,20 @@ def sub_span_paint(o, voice, start, end, outputs, temps, nic, sample_rate, freq,
 FIELDS = ("freq", "color", "note_on")
 
 
-def value(tb, dflt, name, k, v):
-    """field `name` of sub-span k, voice v: the table's array, else the per-voice / broadcast default"""
-    if tb.get(name) is not None:
-        return tb[name][k, v]
-    d = dflt[name]
-    return d[v] if isinstance(d, np.ndarray) else d
-
-
 def paint_spans(o, voices, tb, img, sync, span, sample_rate, zero_first, patch=None, dflt=None):
     """the span paint's contract for every voice over its sub-spans, in place on img and sync [V][rows] (sync None: outputs[1] is
     not painted); a sub-span out of order ends the voice's list; frames no sub-span covers are left alone"""
     S, E = span
     V, rows = img.shape
-    K = tb["start"].shape[0]
     temps = [np.zeros(rows, f32) for _ in range(2)]
     if zero_first:
         img[:, S:E] = 0.0
         if sync is not None:
             sync[:, S:E] = 0.0
     for v in range(V):
-        i = S
-        for k in range(min(int(tb["count"][v]), K)):
-            s, e = int(tb["start"][k, v]), int(tb["end"][k, v])
-            if s < i or s > E:
-                break
-            assert s <= e <= E
+        for k, s, e in walk(tb, v, S, E):
             sub_span_paint(o, voices[v], s, e, (img[v], None if sync is None else sync[v]), temps, tb["nic"][k, v], sample_rate,
                            value(tb, dflt, "freq", k, v), value(tb, dflt, "color", k, v), int(value(tb, dflt, "note_on", k, v)) != 0, patch)
-            i = e
     return img
 
 
