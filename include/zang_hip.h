@@ -533,6 +533,27 @@ ZH_API int zh_decimator_paint(zh_decimator *m, uint32_t span_start, uint32_t spa
                               const zh_buf *temps, zh_bool note_id_changed,
                               const zh_decimator_params *params, uint32_t flags);                     /* :21-57 */
 
+/* The decimated group mix: the bus of examples/example_polyphony.zig (:135-163) for every group at once, ONE kernel.  `m` is a
+ * Decimator of one voice per GROUP of `src` (groups as in zh_mixdown_groups: group g = voices [g*P, (g+1)*P), P = group_voices);
+ * its get_state / set_state are the groups' Decimator states.  For every group g and every frame f of the span
+ *     mix = +0 + src[f][g*P + 0] + ... + src[f][g*P + P-1]       in f32, in that order: the bits of zh_mixdown_groups with
+ *                                                                 ZH_PAINT_ZERO_FIRST (the zeroed temps[2], :135)
+ * and then, onto the row dst[g * dst_stride_floats + f] (start value +0 with ZH_PAINT_ZERO_FIRST, otherwise what dst held):
+ *  - modes[g].bypass != 0:             dst = start + mix (addInto, :162); the Decimator's state is not touched;
+ *  - otherwise exactly Decimator.paint (src/modules/Decimator.zig:34-56) with input = mix, fake_sample_rate =
+ *    modes[g].fake_sample_rate: fake >= sample_rate: dst = start + mix, then the state is reset to dval = 0, dcount = 1;
+ *    fake > 0: the hold (dcount += fake / sample_rate; at dcount >= 1 dval = mix and dcount -= 1; dst = start + dval); anything
+ *    else (zero, negative, NaN): nothing is added and the state is not touched (with ZH_PAINT_ZERO_FIRST the span is +0).
+ *    The comparisons and the quotient are the reference's, so a non-finite rate does what it does there.
+ * Frames outside the span are neither read nor written.  `modes` is device memory, [groups], read by the kernel.  Return codes
+ * and the cases where nothing is launched (no groups, an empty span -- the state is then not reset either) are those of
+ * zh_mixdown_groups; also ZH_ERR_INVALID: a NULL m or modes, m's voice count != src.voices / group_voices.  ZH_ERR_UNSUPPORTED:
+ * ZH_PAINT_TOLERANT.  No sync, no allocation: capturable.  The state is updated in place (no flip of the double buffer). */
+typedef struct zh_group_decimation { float fake_sample_rate; uint32_t bypass; } zh_group_decimation;
+ZH_API int zh_decimator_paint_groups(zh_decimator *m /* n_voices == number of groups */, uint32_t span_start, uint32_t span_end,
+                                     float *dst, size_t dst_stride_floats, zh_buf src, uint32_t group_voices, float sample_rate,
+                                     const zh_group_decimation *modes /* device [groups] */, uint32_t flags);
+
 /* ---------------------------------------------------------------- Distortion (src/modules/Distortion.zig) -- stateless */
 typedef struct zh_distortion zh_distortion;
 enum { ZH_DISTORTION_OVERDRIVE = 0, ZH_DISTORTION_CLIP = 1 };                                         /* :8-11 */
@@ -1334,6 +1355,55 @@ ZH_API int zh_arp_span_param(const zh_arp *arp, uint32_t field /* ZH_ARP_SPAN_* 
 ZH_API int zh_arp_overflows(zh_arp *arp, uint64_t *out);
 ZH_API int zh_arp_get_state(zh_arp *arp, zh_arp_state *host /*[n_players]*/);
 ZH_API int zh_arp_set_state(zh_arp *arp, const zh_arp_state *host);
+
+/* ---------------------------------------------------------------- the key fan-out stage: one always-running voice per key, ON THE DEVICE
+ * Polyphony.paint of examples/example_polyphony.zig (:61-92) without its instruments, for n players of n_keys voices, one lane per
+ * VOICE: a stage between a live voice bank and a voice.  INPUT: exactly zh_arp_schedule's -- the sub-span table a live bank of
+ * polyphony 1 fills from records {held_lo, held_hi, on = 1} (MainModule.paint's Trigger, :137-145; keyEvent :171-176 pushes the
+ * whole held-key mask), as `in` + held[2], and the key frequencies given at creation (1 to 64 f32, copied to the device: the
+ * caller's a4 * rel_freq).  OUTPUT: the stage's own table of n_players * n_keys columns, voice v = player * n_keys + key (the group
+ * layout of zh_mixdown_groups and zh_decimator_paint_groups; n_players * n_keys <= 2^31) -- count, start, end, note_id_changed,
+ * freq, note_on -- read in place through zh_keyfan_span_table (the zh_span_table of zh_nice_paint_spans / zh_pmosc_paint_spans) or
+ * through zh_keyfan_script_table / zh_keyfan_span_param (any other *_paint_spans; field 0 = freq as `f`, 1 = note_on as `u`).
+ * zh_keyfan_schedule enqueues ONE kernel: no sync, no copy, capturable.
+ * Per voice and per outer sub-span [s, e) of its player, in order, with bit = the key's bit of the mask (bits at or above n_keys
+ * belong to no voice) -- not at all where the outer table has no sub-span: state untouched, no rows:
+ *  - bit != down (:70-77): id = next_id++, down = bit, and the impulse (frame 0, id, {freq = key_freqs[key], note_on = bit}) goes to
+ *    the voice's Trigger, which takes it at the walk's position s (frame 0 is below s in every sub-span but a buffer's first: the
+ *    reference asserts, trigger.zig:161; taken at the position, as zh_trigger_next defines it).  s < e: the row (s, e, freq, bit,
+ *    note_id_changed as trigger.zig:96-99: 1 without a carried note, else id != its id), and the note is the carried one.
+ *    s == e (no outer Trigger makes one, a caller's table can): no walk, so no row and the carried note stays; down and next_id have
+ *    advanced and the impulse is lost with the consumed queue.
+ *  - else, with a carried note and s < e: the row (s, e, its freq, its note_on, 0).  Else nothing.
+ * in->count above in->max_spans reads the first in->max_spans rows; a sub-span with end < start or end > out_len ends the
+ * player's list.  The carried note's sample rate is not kept: the voice takes the call's.  OVERFLOW as on a voice bank: a voice's
+ * list stops at max_spans, state advances, zh_keyfan_overflows counts dropped rows; an outer ImpulseQueue holds 32 impulses, so
+ * max_spans >= 34 drops nothing behind a live bank.  Capacity: 4 rows at creation, zh_keyfan_reserve changes it (invalidates views;
+ * ZH_ERR_UNSUPPORTED while a capture records).  zh_keyfan_reset: Voice :50-56 -- all zero, next_id = 1.  set_state takes any
+ * words (`down` is compared as a word, freq is carried as its bits).  ZH_ERR_INVALID: NULL arguments, n_keys outside 1..64,
+ * n_players * n_keys above 2^31, max_spans of 0 or above the capacity, a NULL array in `in` or held, in->max_spans == 0, a field
+ * at or above ZH_KEYFAN_SPAN_FIELDS. */
+typedef struct zh_keyfan zh_keyfan;
+typedef struct zh_keyfan_state {
+    uint64_t next_id;                      /* the Voice's IdGenerator (:37) */
+    uint32_t down;                         /* :35 */
+    uint32_t has_note;                     /* the Voice's Trigger's carried note (:39, trigger.zig:41) ... */
+    uint64_t note_id;
+    float freq; uint32_t note_on;          /* ... and its params */
+} zh_keyfan_state;
+enum { ZH_KEYFAN_SPAN_FREQ = 0 /* f */, ZH_KEYFAN_SPAN_NOTE_ON /* u */, ZH_KEYFAN_SPAN_FIELDS };
+ZH_API int zh_keyfan_create(zh_ctx *ctx, uint32_t n_players, const float *key_freqs /* host [n_keys] */, uint32_t n_keys, zh_keyfan **out);
+ZH_API int zh_keyfan_destroy(zh_keyfan *kf);
+ZH_API int zh_keyfan_reset(zh_keyfan *kf);                                                             /* Voice :50-56 */
+ZH_API int zh_keyfan_reserve(zh_keyfan *kf, uint32_t max_rows);
+ZH_API int zh_keyfan_schedule(zh_keyfan *kf, uint32_t out_len, uint32_t max_spans, const zh_script_span_table *in,
+                              const zh_script_span_param *held /*[2]: held_lo, held_hi*/);             /* :61-92 per outer sub-span */
+ZH_API int zh_keyfan_span_table(const zh_keyfan *kf, uint32_t max_spans, zh_span_table *out);
+ZH_API int zh_keyfan_script_table(const zh_keyfan *kf, uint32_t max_spans, zh_script_span_table *out);
+ZH_API int zh_keyfan_span_param(const zh_keyfan *kf, uint32_t field /* ZH_KEYFAN_SPAN_* */, zh_script_span_param *out);
+ZH_API int zh_keyfan_overflows(zh_keyfan *kf, uint64_t *out);
+ZH_API int zh_keyfan_get_state(zh_keyfan *kf, zh_keyfan_state *host /*[n_players * n_keys]*/);
+ZH_API int zh_keyfan_set_state(zh_keyfan *kf, const zh_keyfan_state *host);
 
 /* ---------------------------------------------------------------- InnerInstrument of the subsong example as ONE fused kernel
  * examples/example_subsong.zig:24-68 for n voices: a TriSawOsc of constant frequency (temps[0], zeroed first) times an Envelope

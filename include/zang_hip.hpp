@@ -646,6 +646,30 @@ public:
     void setState(const State *host) { check(zh_arp_set_state(h_, host), "zh_arp_set_state"); }
 };
 
+// Polyphony.paint of examples/example_polyphony.zig (:61-92) without its instruments, for n players of n_keys always-running voices
+// on the device: a stage between a live voice bank of polyphony 1 (records {held_lo, held_hi, on = 1}) and a voice's span paint;
+// voice = player * n_keys + key
+class KeyFan : public Stage<zh_keyfan, zh_keyfan_destroy, zh_keyfan_reserve, zh_keyfan_script_table, zh_keyfan_span_param, zh_keyfan_overflows> {
+public:
+    using State = zh_keyfan_state;
+    KeyFan(Context &ctx, uint32_t n_players, const float *key_freqs, uint32_t n_keys) : Stage("zh_keyfan") {
+        check(zh_keyfan_create(ctx.get(), n_players, key_freqs, n_keys, &h_), "zh_keyfan_create");
+    }
+    void reset() { check(zh_keyfan_reset(h_), "zh_keyfan_reset"); }                               // Voice :50-56
+    // one buffer: `in` and held[2] are the outer bank's views (zh_voice_bank_script_table, zh_voice_bank_span_param of words 0 and 1)
+    void schedule(uint32_t out_len, uint32_t max_spans, const zh_script_span_table &in, const zh_script_span_param *held) {
+        check(zh_keyfan_schedule(h_, out_len, max_spans, &in, held), "zh_keyfan_schedule");
+    }
+    // the view zh_nice_paint_spans and zh_pmosc_paint_spans take (paintSpans below)
+    zh_span_table spanTable(uint32_t max_spans) const {
+        zh_span_table t{};
+        check(zh_keyfan_span_table(h_, max_spans, &t), "zh_keyfan_span_table");
+        return t;
+    }
+    void getState(State *host) const { check(zh_keyfan_get_state(h_, host), "zh_keyfan_get_state"); }
+    void setState(const State *host) { check(zh_keyfan_set_state(h_, host), "zh_keyfan_set_state"); }
+};
+
 // InnerInstrument of examples/example_subsong.zig (:24-68) for n voices as one fused kernel: a sawtooth of constant frequency
 // times an envelope whose curves are cubed; one output
 class SawEnv {
@@ -863,6 +887,14 @@ ZANG_HIP_MODULE(PMOscInstrument, pmosc, 3, ZANG_HIP_COMMA_F32, ZANG_HIP_USE_F32,
 #undef ZANG_HIP_USE_SEED
 #undef ZANG_HIP_COMMA_F32
 #undef ZANG_HIP_USE_F32
+
+// The decimated group mix (examples/example_polyphony.zig:135-163 for every group): `m` has one voice per group of `src`; group g's
+// voices are added in order from +0 and go through its Decimator -- or straight on, modes_dev[g].bypass -- onto row g of dst_dev
+inline void paintGroups(Decimator &m, zang::Span span, float *dst_dev, size_t dst_stride_floats, zh_buf src, uint32_t group_voices,
+                        float sample_rate, const zh_group_decimation *modes_dev, uint32_t flags = ZH_PAINT_ADD) {
+    zang::check(zh_decimator_paint_groups(m.get(), span.start, span.end, dst_dev, dst_stride_floats, src, group_voices, sample_rate, modes_dev, flags),
+                "zh_decimator_paint_groups");
+}
 
 // The Sampler over a sample kit: the sample and the channel are per-voice / per-note values like the rate and the loop flag
 // (Sampler.zig:62-67).  paintKit: n Samplers, each with its own sample, over one span; paintKitSpans: the Trigger loop, span_params

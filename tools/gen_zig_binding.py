@@ -68,6 +68,8 @@ MANY_SPECIAL = {("zh_script_module_paint", "params"), ("zh_polyphony_dispatcher_
                 ("zh_hard_square_paint_spans", "span_params"),
                 # two entries: held_lo, held_hi; n_keys frequencies
                 ("zh_arp_schedule", "held"), ("zh_arp_create", "key_freqs"),
+                # the same two and n_keys; one record per group
+                ("zh_keyfan_schedule", "held"), ("zh_keyfan_create", "key_freqs"), ("zh_decimator_paint_groups", "modes"),
                 ("zh_saw_env_paint_spans", "span_params"),
                 # three entries: freq, note_on, melody; n_melodies + 1 offsets, n_events events
                 ("zh_subsong_schedule", "outer"), ("zh_melody_kit_create", "offsets"), ("zh_melody_kit_create", "events"),

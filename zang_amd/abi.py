@@ -351,6 +351,17 @@ class ArpState(C.Structure):               # zh_arp_state: examples/example_arpe
 ARP_SPAN_FREQ, ARP_SPAN_NOTE_ON, ARP_SPAN_FIELDS = range(3)
 
 
+class KeyFanState(C.Structure):            # zh_keyfan_state: Voice of examples/example_polyphony.zig:34-40 without the instrument
+    _fields_ = [("next_id", u64), ("down", u32), ("has_note", u32), ("note_id", u64), ("freq", f32), ("note_on", u32)]
+
+
+KEYFAN_SPAN_FREQ, KEYFAN_SPAN_NOTE_ON, KEYFAN_SPAN_FIELDS = range(3)
+
+
+class GroupDecimation(C.Structure):        # zh_group_decimation
+    _fields_ = [("fake_sample_rate", f32), ("bypass", u32)]
+
+
 class SawEnvPatch(C.Structure):            # zh_saw_env_patch: the constants of examples/example_subsong.zig:55-63
     _fields_ = [("color", f32), ("attack", f32), ("decay", f32), ("release", f32), ("sustain_volume", f32)]
 
@@ -631,6 +642,7 @@ SIGNATURES = {
     "zh_decimator_get_state": (C.c_int, [vp, vp]),
     "zh_decimator_set_state": (C.c_int, [vp, vp]),
     "zh_decimator_paint": (C.c_int, _paint(DecimatorParams)),
+    "zh_decimator_paint_groups": (C.c_int, [vp, u32, u32, vp, C.c_size_t, Buf, u32, f32, vp, u32]),
     "zh_distortion_create": (C.c_int, [vp, u32, P(vp)]),
     "zh_distortion_destroy": (C.c_int, [vp]),
     "zh_distortion_paint": (C.c_int, _paint(DistortionParams)),
@@ -788,6 +800,17 @@ SIGNATURES = {
     "zh_arp_overflows": (C.c_int, [vp, P(u64)]),
     "zh_arp_get_state": (C.c_int, [vp, vp]),
     "zh_arp_set_state": (C.c_int, [vp, vp]),
+    "zh_keyfan_create": (C.c_int, [vp, u32, vp, u32, P(vp)]),
+    "zh_keyfan_destroy": (C.c_int, [vp]),
+    "zh_keyfan_reset": (C.c_int, [vp]),
+    "zh_keyfan_reserve": (C.c_int, [vp, u32]),
+    "zh_keyfan_schedule": (C.c_int, [vp, u32, u32, P(ScriptSpanTable), P(ScriptSpanParam)]),
+    "zh_keyfan_span_table": (C.c_int, [vp, u32, P(SpanTable)]),
+    "zh_keyfan_script_table": (C.c_int, [vp, u32, P(ScriptSpanTable)]),
+    "zh_keyfan_span_param": (C.c_int, [vp, u32, P(ScriptSpanParam)]),
+    "zh_keyfan_overflows": (C.c_int, [vp, P(u64)]),
+    "zh_keyfan_get_state": (C.c_int, [vp, vp]),
+    "zh_keyfan_set_state": (C.c_int, [vp, vp]),
     "zh_saw_env_patch_default": (C.c_int, [P(SawEnvPatch)]),
     "zh_saw_env_create": (C.c_int, [vp, u32, P(vp)]),
     "zh_saw_env_destroy": (C.c_int, [vp]),

@@ -151,6 +151,10 @@ void zh_flipper_unregister(zh_flipper *f);
 void zh_flipper_used(zh_flipper *f);         // call at the start of EVERY paint of a flipper module (in-place forms too)
 void zh_flipper_painted(zh_flipper *f);      // call right BEFORE flipping f->cur in a paint
 
+// mix_groups.hip: the group mix with a Decimator per group behind it, for zh_decimator_paint_groups (modules.hip); m: a zh_decimator
+int zh_decimated_groups_launch(zh_flipper *m, uint32_t start, uint32_t end, float *dst, size_t dst_stride_floats, zh_buf src, uint32_t group_voices,
+                               float sample_rate, const zh_group_decimation *modes, uint32_t flags);
+
 // dispatch.hip: the ONE table of form-selecting thresholds and range counts (rows in the order of this enum); zh_form = a row's
 // value (its default, or the ZH_FORMS override); zh_range_frames = frames per range for a kernel that paints a span as several
 // frame ranges at once, each replaying the cheap state walk of the frames before it (0 = paint sequentially): row `form` = number

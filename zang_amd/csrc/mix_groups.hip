@@ -32,10 +32,10 @@ struct MgPcm {
     float mul;
 };
 
+// group tile gt, frame tile ft
 template <class Init, class Emit>
-__device__ __forceinline__ void mg_tile(const MgArgs &a, float *tile, Init init, Emit emit) {
+__device__ __forceinline__ void mg_tile(const MgArgs &a, float *tile, uint32_t gt, uint32_t ft, Init init, Emit emit) {
     const uint32_t tid = threadIdx.x, fl = tid % kMgFrames, w = tid / kMgFrames;
-    const uint32_t gt = blockIdx.x % a.n_gtiles, ft = blockIdx.x / a.n_gtiles;
     const uint32_t g0 = gt * a.G, ng = min(a.G, a.n_groups - g0);
     const uint32_t f0 = a.f_base + ft * kMgFrames;                       // < a.end: the tile exists
     const uint32_t r_lo = a.start > f0 ? a.start - f0 : 0u, r_hi = min(a.end - f0, kMgFrames);   // the tile's rows inside the span
@@ -91,14 +91,14 @@ __device__ __forceinline__ void mg_tile(const MgArgs &a, float *tile, Init init,
 
 __global__ void __launch_bounds__(kMgBlock) k_mix_groups(MgArgs a, float *__restrict__ dst, size_t dst_stride, int zero_first) {
     __shared__ float tile[kMgFrames * kMgPitch];
-    mg_tile(a, tile,
+    mg_tile(a, tile, blockIdx.x % a.n_gtiles, blockIdx.x / a.n_gtiles,
             [&](uint32_t g, uint32_t f) { return zero_first ? 0.0f : dst[(size_t)g * dst_stride + f]; },
             [&](uint32_t g, uint32_t f, uint32_t, float s, bool ok) { if (ok) dst[(size_t)g * dst_stride + f] = s; });
 }
 
 __global__ void __launch_bounds__(kMgBlock) k_mix_groups_pcm(MgArgs a, MgPcm o) {
     __shared__ float tile[kMgFrames * kMgPitch];
-    mg_tile(a, tile,
+    mg_tile(a, tile, blockIdx.x % a.n_gtiles, blockIdx.x / a.n_gtiles,
             [&](uint32_t g, uint32_t f) { return o.acc ? o.acc[(size_t)g * o.acc_stride + f] : 0.0f; },
             [&](uint32_t g, uint32_t f, uint32_t fl, float s, bool ok) {
                 const int32_t c = zm_pcm(s, o.mul, o.s16 != 0);
@@ -125,7 +125,79 @@ __global__ void __launch_bounds__(kMgBlock) k_mix_groups_pcm(MgArgs a, MgPcm o) 
             });
 }
 
-// the checks both entry points share; *n_groups = 0: nothing to do
+// The group mix with a Decimator per group behind it (zh_decimator_paint_groups): examples/example_polyphony.zig:135-163 for every
+// group -- the zeroed temps[2] the voices are added onto, then Decimator.paint (src/modules/Decimator.zig:34-56) or addInto (:162)
+// onto the output.  A workgroup keeps its G groups and walks the span's frame tiles IN ORDER: what goes from frame to frame is the
+// Decimator's counter alone (dcount += ratio, :46-50), which reads no sample.  Per tile thread j < G (the owner of group g0 + j's
+// counter for the whole launch, in a register) runs the tile's counter steps and leaves the frames that sample as a 64-bit mask in
+// LDS; the frame lanes add their group's voices as in k_mix_groups; each then takes dval from the sum of the highest sampling
+// frame at or below its own (a ds_bpermute within the wave: a wave holds one group's 64 frames) or, with none, the dval carried in
+// LDS, which the lane of the tile's last sampling frame then replaces.  mode: Decimator.zig:34 (0: addInto and reset), :39 (1: the
+// hold), neither (2: nothing painted), and 3 = the example's bypass (:161-163: addInto, the Decimator not touched).
+struct MgDec {
+    float *dst; size_t dst_stride;
+    const zh_group_decimation *modes;       // [n_groups]
+    float *dval, *dcount;                   // [n_groups] each, updated in place: a group belongs to one workgroup
+    float sample_rate;
+    int zero_first;
+};
+__global__ void __launch_bounds__(kMgBlock) k_mix_groups_decimated(MgArgs a, MgDec d) {
+    __shared__ float tile[kMgFrames * kMgPitch];
+    __shared__ unsigned long long s_mask[kMgCols];
+    __shared__ float s_dval[kMgCols];
+    __shared__ uint32_t s_mode[kMgCols];
+    const uint32_t tid = threadIdx.x, gt = blockIdx.x, g0 = gt * a.G, ng = min(a.G, a.n_groups - g0);
+    uint32_t mode = 3;
+    float ratio = 0.0f, dcount = 0.0f;
+    if (tid < ng) {
+        const zh_group_decimation md = d.modes[g0 + tid];
+        mode = md.bypass ? 3u : md.fake_sample_rate >= d.sample_rate ? 0u : md.fake_sample_rate > 0.0f ? 1u : 2u;   // :34, :39
+        ratio = md.fake_sample_rate / d.sample_rate;                                                                 // :40
+        dcount = d.dcount[g0 + tid];
+        s_dval[tid] = d.dval[g0 + tid];
+        s_mode[tid] = mode;
+    }
+    const uint32_t n_ft = (a.end - a.f_base + kMgFrames - 1) / kMgFrames;
+    for (uint32_t ft = 0; ft < n_ft; ft++) {
+        if (mode == 1) {                                                 // (tid < ng) :45-50 without the sample
+            const uint32_t f0 = a.f_base + ft * kMgFrames;
+            const uint32_t r_lo = a.start > f0 ? a.start - f0 : 0u, r_hi = min(a.end - f0, kMgFrames);
+            unsigned long long mask = 0;
+            for (uint32_t r = r_lo; r < r_hi; r++) {
+                const float dc = dcount + ratio;
+                const bool trig = dc >= 1.0f;
+                dcount = trig ? dc - 1.0f : dc;
+                mask |= (unsigned long long)trig << r;
+            }
+            s_mask[tid] = mask;
+        }
+        // (mg_tile's barrier between its loads and its sums stands between the stores above and the reads below; the one after its
+        // sums between those reads and the next tile's stores)
+        mg_tile(a, tile, gt, ft,
+                [&](uint32_t, uint32_t) { return 0.0f; },                // the zeroed temps[2], :135
+                [&](uint32_t g, uint32_t f, uint32_t fl, float m, bool ok) {
+                    const uint32_t j = g - g0, md = s_mode[j];           // (the same for every lane of the wave)
+                    float val = m;
+                    if (md == 1) {
+                        const unsigned long long mask = s_mask[j], below = mask & (~0ull >> (63u - fl));
+                        const float carried = s_dval[j];
+                        const float held = __shfl(m, below ? 63 - __builtin_clzll(below) : (int)fl);
+                        val = below ? held : carried;
+                        if (mask && fl == 63u - (uint32_t)__builtin_clzll(mask)) s_dval[j] = m;   // after the wave's reads of it
+                    }
+                    if (!ok) return;
+                    float *o = d.dst + (size_t)g * d.dst_stride + f;
+                    if (md == 2) { if (d.zero_first) *o = 0.0f; }
+                    else *o = (d.zero_first ? 0.0f : *o) + val;          // output[i] += ..., :51 / addInto
+                });
+    }
+    if (tid < ng) {                                                      // (mg_tile ends on a barrier: s_dval is final)
+        if (mode == 1) { d.dval[g0 + tid] = s_dval[tid]; d.dcount[g0 + tid] = dcount; }   // :54-55
+        else if (mode == 0) { d.dval[g0 + tid] = 0.0f; d.dcount[g0 + tid] = 1.0f; }       // :37-38
+    }
+}
+
+// the checks the entry points share; *n_groups = 0: nothing to do
 int mg_prepare(zh_ctx *ctx, uint32_t start, uint32_t end, const void *dst, const zh_buf &src, uint32_t P, MgArgs *a, uint64_t *blocks) {
     if (!ctx || !dst || P == 0 || !src.ptr || src.voices % P != 0 || end < start || !buf_covers(src, src.voices, end)) return ZH_ERR_INVALID;
     a->src = src.ptr; a->stride = src.stride; a->P = P;
@@ -140,6 +212,23 @@ int mg_prepare(zh_ctx *ctx, uint32_t start, uint32_t end, const void *dst, const
     return *blocks > 0x7fffffffull ? ZH_ERR_INVALID : ZH_OK;
 }
 }  // namespace
+
+// zh_decimator_paint_groups (modules.hip, where zh_decimator is defined) behind its NULL check
+int zh_decimated_groups_launch(zh_flipper *m, uint32_t start, uint32_t end, float *dst, size_t dst_stride_floats, zh_buf src, uint32_t group_voices,
+                               float sample_rate, const zh_group_decimation *modes, uint32_t flags) {
+    MgArgs a;
+    uint64_t blocks;
+    int rc = mg_prepare(m->ctx, start, end, dst, src, group_voices, &a, &blocks);
+    if (rc) return rc;
+    if ((a.n_groups > 1 && dst_stride_floats < end) || m->n != a.n_groups || (a.n_groups && !modes)) return ZH_ERR_INVALID;
+    if (flags & ZH_PAINT_TOLERANT) return ZH_ERR_UNSUPPORTED;
+    if (a.n_groups == 0 || end == start) return ZH_OK;
+    zh_flipper_used(m);                     // a capture must know the state buffer this paint starts from (ctx.hip); in place: no flip
+    float *state = reinterpret_cast<float *>(m->cnt[m->cur]);                                  // [dval n][dcount n]
+    const MgDec d{dst, dst_stride_floats, modes, state, state + m->n, sample_rate, (int)(flags & ZH_PAINT_ZERO_FIRST)};
+    ZH_LAUNCH(k_mix_groups_decimated, dim3(a.n_gtiles), dim3(kMgBlock), 0, m->ctx->stream, a, d);
+    return zh_launch_status();
+}
 
 extern "C" {
 

@@ -1998,6 +1998,11 @@ int zh_decimator_paint(zh_decimator *m, uint32_t start, uint32_t end, const zh_b
                  mk_cimg(p->input), start, end, p->sample_rate, mk_f32(p->fake_sample_rate));
     return zh_launch_status();
 }
+int zh_decimator_paint_groups(zh_decimator *m, uint32_t start, uint32_t end, float *dst, size_t dst_stride_floats, zh_buf src, uint32_t group_voices,
+                              float sample_rate, const zh_group_decimation *modes, uint32_t flags) { ZH_GUARD(m ? m->ctx : nullptr);
+    if (!m) return ZH_ERR_INVALID;
+    return zh_decimated_groups_launch(m, start, end, dst, dst_stride_floats, src, group_voices, sample_rate, modes, flags);   // mix_groups.hip
+}
 
 // ------------------------------------------------------------------ Curve
 int zh_curve_module_create(zh_ctx *ctx, uint32_t n, zh_curve_module **out) { ZH_GUARD(ctx); return flip_create<CurveModuleLayout>(ctx, n, out); }   // init() :46-54

@@ -14,6 +14,7 @@ from dataclasses import dataclass
 from typing import Any
 
 import numpy as np
+import torch
 
 from . import abi
 from .runtime import as_bool, as_buf, as_f32, as_u32, default_context
@@ -406,6 +407,27 @@ class Decimator(_Module):
 
     def paint(self, span, outputs, temps, note_id_changed, params, zero_first=False):
         self._paint(span, outputs, temps, note_id_changed, self._cparams(params), zero_first)
+
+    def _paint_groups(self, span, dst, src, group_voices, sample_rate, modes, flags):
+        """-> the return code of zh_decimator_paint_groups"""
+        return self.lib.zh_decimator_paint_groups(self.handle, span.start, span.end, dst.data_ptr(), dst.stride(0), as_buf(src), group_voices,
+                                                  float(sample_rate), modes.data_ptr(), flags)
+
+    def paint_groups(self, span, dst, src, group_voices, sample_rate, modes, zero_first=False):
+        """The decimated group mix (zh_decimator_paint_groups), this module one voice per group: every group of `group_voices`
+        consecutive voices of `src` added in voice order from +0, then through its Decimator -- or straight on where its mode is a
+        bypass -- onto dst[g] (float32 CUDA tensor [groups, >= span.end]).  `modes`: a CUDA uint8 tensor holding [groups]
+        abi.GroupDecimation records (group_modes())."""
+        assert dst.dtype == torch.float32 and dst.dim() == 2 and dst.stride(1) == 1 and dst.shape[0] == self.n_voices
+        assert modes.is_cuda and modes.is_contiguous() and modes.numel() * modes.element_size() == self.n_voices * C.sizeof(abi.GroupDecimation)
+        abi.check(self._paint_groups(span, dst, src, group_voices, sample_rate, modes, abi.PAINT_ZERO_FIRST if zero_first else abi.PAINT_ADD),
+                  "zh_decimator_paint_groups")
+
+    def group_modes(self, fake_sample_rates, bypass):
+        """[groups] rates and bypass flags -> the device array paint_groups takes (a copy from the host)"""
+        rec = np.zeros(self.n_voices, np.dtype(abi.GroupDecimation))
+        rec["fake_sample_rate"], rec["bypass"] = fake_sample_rates, bypass
+        return torch.from_numpy(rec.view(np.uint8).copy()).to(self.ctx.device)
 
 
 class Distortion(_Module):
